@@ -204,7 +204,16 @@ def main():
     ap.add_argument("--readback", action="store_true",
                     help="stream a snapshot of all agents to pinned host memory every step (the "
                          "PCIe-inclusive rate; not the headline value)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline leg's timed steps, write the crowd its last step computed (ascending id) "
+                         "as DIR/<field>.npy in float64, outside the clock; a fixed seeded sample of the agents above "
+                         "64 MB in all.  With the same arguments the inputs are the same from run to run, so two builds "
+                         "compare output for output.  --gpus > 1: --mesh native only")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1 and args.mesh != "native":
+        ap.error("--dump-outputs with --gpus > 1 needs --mesh native (cs_mesh_read_agents gathers the whole crowd)")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     launch_ranks_if_needed(args)  # --gpus N without a launcher: start the N ranks as a child and exit with its code
 
     import torch
@@ -315,7 +324,8 @@ def main():
         line["fallback"] = "the overlapped headline leg did not finish: this is the short leg WITHOUT the overlap that ran before it"
         progress["line"] = json.dumps(line)
         arm("headline leg (" + args.scaling + " scaling)")
-    main_leg = run_leg(args, ctx, args.scaling, args.steps, args.warmup, args.clock_warmup, headline=True)
+    main_leg = run_leg(args, ctx, args.scaling, args.steps, args.warmup, args.clock_warmup, headline=True,
+                       dump_dir=args.dump_outputs)
     other_leg = None
     if world > 1 and not args.no_second_scaling_leg:
         line = dict(main_leg["line"]) if rank == 0 else {}
@@ -471,10 +481,30 @@ def verify_mesh(args, ctx, stepper, mesh_kind, steps_made, fill, single_engine, 
     return verdict[0]
 
 
-def run_leg(args, ctx, scaling, steps, warmup, clock_warmup_min, headline, overlap=None):
+DUMP_MAX_BYTES = 64 << 20
+DUMP_FIELDS = ("id", "x", "y", "vx", "vy", "next_waypoint")
+
+
+def dump_outputs(dump_dir, crowd):
+    """The crowd a step left (read_agents: ascending id) as dump_dir/<field>.npy, float64 (ids and waypoint indices are
+    exact below 2^53).  Above DUMP_MAX_BYTES in all, the same seeded sample of rows is kept every run."""
+    per_agent = 8 * len(DUMP_FIELDS)
+    n = len(crowd)
+    sampled = n * per_agent > DUMP_MAX_BYTES
+    if sampled:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // per_agent, replace=False))
+        crowd = crowd[keep]
+    os.makedirs(dump_dir, exist_ok=True)
+    for name in DUMP_FIELDS:
+        np.save(os.path.join(dump_dir, name + ".npy"), crowd[name].astype(np.float64))
+    print(f"bench: --dump-outputs: {len(crowd)} of {n} agents x {DUMP_FIELDS} -> {dump_dir}"
+          + (" (seeded sample)" if sampled else ""), file=sys.stderr, flush=True)
+
+
+def run_leg(args, ctx, scaling, steps, warmup, clock_warmup_min, headline, overlap=None, dump_dir=None):
     """One timed run of `steps` steps (after `warmup` + clock warm-up untimed ones) under `scaling`.
     headline=True also builds the JSON line (roofline, creep leg, CPU baselines).  overlap: CS_CFG_TILE_OVERLAP for this
-    leg's mesh (default: args.overlap)."""
+    leg's mesh (default: args.overlap).  dump_dir: the crowd after the last timed step goes there (dump_outputs)."""
     overlap = args.overlap if overlap is None else overlap
     torch, dist = ctx["torch"], ctx["dist"]
     rank, world, device, backend = ctx["rank"], ctx["world"], ctx["device"], ctx["backend"]
@@ -668,6 +698,19 @@ def run_leg(args, ctx, scaling, steps, warmup, clock_warmup_min, headline, overl
             drain()  # surfaces "Index out of bounds" if any step left the grid
     except Exception as err:  # noqa: BLE001
         fail(f"{leg_name}: a step of the timed region failed", err)
+    if dump_dir:
+        # what the last timed step computed, before the report step below moves the crowd on (a native mesh gathers
+        # the whole crowd on every rank: a collective)
+        arm(f"{leg_name}: --dump-outputs")
+        try:
+            if mesh_kind not in (None, "native"):
+                raise RuntimeError("needs a single engine or the native mesh, the run is on the " + mesh_kind + " mesh")
+            crowd = stepper.read_agents()
+            if rank == 0:
+                dump_outputs(dump_dir, crowd)
+            del crowd
+        except Exception as err:  # noqa: BLE001
+            fail(f"{leg_name}: --dump-outputs", err)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
     if world > 1:

@@ -1,4 +1,5 @@
 #!/bin/bash
+ROOT=$(cd "$(dirname "$0")/.." && pwd)  # the repository this script belongs to
 # usage: tools/abl_variants.sh build            (here: one build of the engine per ablation, compile-time switches)
 #        tools/abl_variants.sh run [bench args] (under gpurun: kernel time of each)
 # -DCS_TILE_ABL=<bits> compiles the tiled kernel WITHOUT the parts named by the bits (unlike the run-time switches of
@@ -7,7 +8,7 @@
 #   64 = no forces, 32 = the older form of the time-to-collision pass, 0 = the product
 BITS=${CS_ABL_BITS:-"0 1 16 8 64 32"}  # 32 = the older time-to-collision pass (per-entry masks) instead of the lean one
 if [ "$1" = build ]; then
-  for d in $BITS; do bash /root/repo/tools/build_variant.sh abl$d -DCS_TILE_ABL=$d || exit 1; done
+  for d in $BITS; do bash $ROOT/tools/build_variant.sh abl$d -DCS_TILE_ABL=$d || exit 1; done
   exit 0
 fi
 shift
