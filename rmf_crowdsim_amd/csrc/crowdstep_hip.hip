@@ -509,8 +509,11 @@ static size_t radius_query(cs_engine* e, double radius, double x, double y, std:
   lx = std::max(lx, -1ll); ly = std::max(ly, -1ll);
   hx = std::min(hx, (long long)(e->ncells / std::max<uint64_t>(e->nx, 1)));
   hy = std::min(hy, every_alias ? (long long)e->ncells : (long long)e->nx * 2);
-  // query point relative to a reference cell: the cell of the point clamped into the grid
-  long long qx = std::min(std::max(fl(x, e->grid.offset_x), 0ll), (long long)e->nx - 1);
+  // query point relative to a reference cell: the cell of the point clamped into the grid (x into its rows: on a grid
+  // taller than wide, clamped into the first nx rows the reference cell lay up to the grid's height away, and the f32
+  // offset of the query from it lost the bits that decide membership at the radius)
+  long long qx = std::min(std::max(fl(x, e->grid.offset_x), 0ll),
+                          std::max((long long)(e->ncells / std::max<uint64_t>(e->nx, 1)) - 1, 0ll));
   long long qy = std::min(std::max(fl(y, e->grid.offset_y), 0ll), (long long)e->nx - 1);
   float qox = (float)((x - e->grid.offset_x) - (double)qx * e->grid.cell_size);
   float qoy = (float)((y - e->grid.offset_y) - (double)qy * e->grid.cell_size);

@@ -996,8 +996,9 @@ struct cs_engine {
     } else {
       hipLaunchKernelGGL(k_scan_totals, dim3(n_scan_blocks), dim3(SCAN_BLOCK), 0, stream, cell_count,
                          (uint32_t)ncells, block_totals);
+      hipLaunchKernelGGL(k_scan_bases, dim3(1), dim3(SCAN_BASES_BLOCK), 0, stream, block_totals, n_scan_blocks);
       hipLaunchKernelGGL(k_scan_apply, dim3(n_scan_blocks), dim3(SCAN_BLOCK), 0, stream, cell_count,
-                         (uint32_t)ncells, block_totals, n_scan_blocks, cell_start, ctr, scan_clears);
+                         (uint32_t)ncells, block_totals, cell_start, ctr, scan_clears);
     }
     // (kept windows: the scan clears the counters of the array the builder workgroups of this step fill.  A sort BETWEEN
     // two steps, for a query or a read, must leave the windows the next step will run on alone: windows_valid is still

@@ -51,8 +51,8 @@ __global__ void k_append_spawns(AgentArrays a, uint32_t slot_cap, const SpawnRec
 
 // ---------------------------------------------------------------------------
 // K2: exclusive scan of cell_count -> cell_start (and zero cell_count)
-//   pass A: per-block totals; pass B: block offset by summing earlier totals,
-//   then an in-block scan.  1024 cells per block.
+//   pass A: per-block totals; pass B: one workgroup turns the totals into block offsets
+//   (an exclusive scan, in place); pass C: an in-block scan from the block's offset.  1024 cells per block.
 // ---------------------------------------------------------------------------
 #define SCAN_BLOCK 256
 #define SCAN_ITEMS 4
@@ -90,30 +90,55 @@ __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_totals(const uint32_t* __re
   }
 }
 
+// Pass B: block_totals -> the offset of every block (exclusive scan, in place), ONE workgroup.  Thread t adds up a run of
+// ceil(nblocks / 1024) totals rounded up to whole uint4s, the runs' sums are scanned across the workgroup, and every
+// thread writes its run's prefixes.  Linear in the blocks: k_scan_apply used to add up all earlier totals in every
+// block, O(blocks^2) loads (~0.5 s a step at the 2.1M blocks of a grid near the 31-bit cell limit).
+#define SCAN_BASES_BLOCK 1024
+__global__ void __launch_bounds__(SCAN_BASES_BLOCK) k_scan_bases(uint32_t* __restrict__ block_totals, uint32_t nblocks) {
+  __shared__ uint32_t wsum[SCAN_BASES_BLOCK / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t run = ((nblocks + SCAN_BASES_BLOCK - 1) / SCAN_BASES_BLOCK + 3u) & ~3u;
+  const uint32_t lo = min(threadIdx.x * run, nblocks), hi = min(lo + run, nblocks);  // (lo: a multiple of 4)
+  uint32_t s = 0;
+  for (uint32_t i = lo; i < hi; i += SCAN_ITEMS) {
+    if (i + SCAN_ITEMS <= hi) {
+      const uint4 q = *reinterpret_cast<const uint4*>(block_totals + i);
+      s += q.x + q.y + q.z + q.w;
+    } else {
+      for (uint32_t k = i; k < hi; ++k) s += block_totals[k];
+    }
+  }
+  const uint32_t incl = wave_incl_scan(s, lane);
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  uint32_t base = incl - s;
+  for (int w = 0; w < wave; ++w) base += wsum[w];
+  for (uint32_t i = lo; i < hi; i += SCAN_ITEMS) {
+    if (i + SCAN_ITEMS <= hi) {
+      const uint4 q = *reinterpret_cast<const uint4*>(block_totals + i);
+      const uint32_t o1 = base + q.x, o2 = o1 + q.y, o3 = o2 + q.z;
+      *reinterpret_cast<uint4*>(block_totals + i) = make_uint4(base, o1, o2, o3);
+      base = o3 + q.w;
+    } else {
+      for (uint32_t k = i; k < hi; ++k) {
+        const uint32_t t = block_totals[k];
+        block_totals[k] = base;
+        base += t;
+      }
+    }
+  }
+}
+
 __global__ void __launch_bounds__(SCAN_BLOCK) k_scan_apply(uint32_t* __restrict__ cell_count,
                                                            uint32_t ncells,
-                                                           const uint32_t* __restrict__ block_totals,
-                                                           uint32_t nblocks,
+                                                           const uint32_t* __restrict__ block_bases,
                                                            uint32_t* __restrict__ cell_start,
                                                            Counters* __restrict__ ctr,
                                                            uint32_t* __restrict__ n_blocks) {
   __shared__ uint32_t wsum[SCAN_BLOCK / 64];
-  __shared__ uint32_t s_base;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // offset of this block = sum of the totals of the blocks before it
-  uint32_t part = 0;
-  for (uint32_t b = threadIdx.x; b < blockIdx.x; b += SCAN_BLOCK) part += block_totals[b];
-  for (int d = 32; d > 0; d >>= 1) part += __shfl_down(part, d, 64);
-  if (lane == 0) wsum[wave] = part;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < SCAN_BLOCK / 64; ++w) t += wsum[w];
-    s_base = t;
-  }
-  __syncthreads();
-  const uint32_t block_base = s_base;
-  __syncthreads();
+  const uint32_t block_base = block_bases[blockIdx.x];  // (k_scan_bases)
 
   uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_ITEMS;
   uint32_t v[SCAN_ITEMS];
