@@ -81,6 +81,13 @@ typedef struct cs_device_cfg {
                                  * band within one step fails the step (it would miss the exchange): one that
                                  * moves more than a cell per step, or whose position turns NaN (the reference
                                  * bins NaN to cell 0, location_hash_2d.rs:54-66, which on a tile is a ghost cell). */
+#define CS_CFG_WIDE_IDS 16u     /* 64-bit agent ids without a lifetime limit (lib.rs:36,83: AgentId = usize).  Without it the
+                                 * engine's ids end at 2^31 ("agent id space exhausted").  With it every id that crosses
+                                 * the ABI is an EXTERNAL u64 id; the device keeps 32-bit ids and, when they run out,
+                                 * renumbers the live agents in place (order and parity kept, so the model is
+                                 * unchanged); an allocation is refused only when twice the live count plus the
+                                 * allocation exceeds the device id space.  On a mesh (cs_mesh_create) all tiles renumber together;
+                                 * a tile engine driven by hand never renumbers by itself. */
 
 /* Zanlungo::new(agent_scale, obstacle_scale, reaction_time, force_distance,
  *               agent_mass, agent_radius)   local_planners/zanlungo.rs:31-48 */
@@ -298,7 +305,9 @@ void cs_event_recording(cs_engine*, int on);
  *       cs_snapshot_request from now
  *   1 = nothing was requested, 2 = not complete yet (only with wait == 0),
  *   3 = device error (cs_last_error)
- * Agents come in no particular order (cs_read_agents sorts by id).            */
+ * Agents come in no particular order (cs_read_agents sorts by id).
+ * Under CS_CFG_WIDE_IDS `id` is the low 32 bits of the agent's external id: unique among the live agents unless one
+ * of them outlives 2^32 later allocations; cs_read_agents gives the full id.                                   */
 typedef struct cs_snapshot_record {
   double x, y;
   float vx, vy;
@@ -355,6 +364,9 @@ uint64_t cs_device_bytes(cs_engine*);
  * tile their band completely, with room to spare, so they stay correct while the agents move one step).  The environment
  * variable CS_WINDOWS_KEEP is a switch, not a period: 0 = cut every step's windows in its own scatter launch */
 #define CS_STAT_STEPS_ON_KEPT_WINDOWS 4u
+/* CS_CFG_WIDE_IDS: renumberings of the device ids so far, and the host wall time spent inside them (ns) */
+#define CS_STAT_RENUMBERINGS 5u
+#define CS_STAT_RENUMBER_NS 6u
 uint64_t cs_kernel_stat(cs_engine*, uint32_t which);
 
 /* ---- measurement (bench.py / rocprof cross-check) ---------------------- */

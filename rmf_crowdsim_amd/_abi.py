@@ -12,11 +12,14 @@ CS_CFG_FORCE_GATHER = 1
 CS_CFG_FORCE_TILED = 2
 CS_CFG_DENSE = 4
 CS_CFG_TILE_OVERLAP = 8
+CS_CFG_WIDE_IDS = 16
 CS_STAT_WINDOWS_OFF_LDS = 0
 CS_STAT_WINDOWS_CHUNKED = 1
 CS_STAT_EXCHANGES_AHEAD = 2
 CS_STAT_EXCHANGES_AHEAD_USED = 3
 CS_STAT_STEPS_ON_KEPT_WINDOWS = 4
+CS_STAT_RENUMBERINGS = 5
+CS_STAT_RENUMBER_NS = 6
 
 CS_HLP_NONE, CS_HLP_CONSTANT, CS_HLP_ID_PARITY, CS_HLP_CALLBACK, CS_HLP_ROUTE = 0, 1, 2, 3, 4
 CS_ROUTE_MAX_WAYPOINTS = 1023

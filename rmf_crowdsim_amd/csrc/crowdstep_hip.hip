@@ -11,6 +11,7 @@
 //   cs_kernels_step.hip.inc   k_step_tiled / k_step_gather: neighbour query + Zanlungo +
 //                             integrate + re-bin + waypoint/sink test
 //                             (location_hash_2d.rs:240-258, zanlungo.rs:49-217, lib.rs:259-359)
+//   cs_kernels_ids.hip.inc    CS_CFG_WIDE_IDS: external ids, the renumbering of device ids (radix sort)
 //   cs_kernels_aux.hip.inc    k_halo_pack/unpack (tiles), k_spawn (lib.rs:199-254), radius query
 //   cs_engine.hip.inc         the host engine: step state machine, tables, tiles, events
 //   cs_rccl.hip.inc           RCCL bound at first use (halo transport of a tile)
@@ -47,6 +48,7 @@
 
 #include "cs_device_types.hip.inc"
 #include "cs_kernels_sort.hip.inc"
+#include "cs_kernels_ids.hip.inc"
 #include "cs_kernels_step.hip.inc"
 #include "cs_kernels_aux.hip.inc"
 #include "cs_engine.hip.inc"
@@ -77,6 +79,7 @@ void cs_destroy(cs_engine* e) {
   e->free_arrays(e->buf[0]);
   e->free_arrays(e->buf[1]);
   hipFree(e->pref); hipFree(e->cell_count); hipFree(e->cell_start); hipFree(e->block_totals);
+  hipFree(e->ext_tab_dev[0]); hipFree(e->ext_tab_dev[1]); hipFree(e->ids_scratch);
   hipFree(e->ctr); hipHostFree(e->ctr_host); hipFree(e->epi_dev); delete[] e->epi_host; hipFree(e->destroyed); hipFree(e->wp_events);
   for (auto& sn : e->snap) {
     if (sn.in_flight) hipEventSynchronize(sn.copied);
@@ -196,6 +199,10 @@ cs_engine* cs_create(const cs_grid_desc* grid, const cs_device_cfg* cfg) {
   if (const char* v = getenv("CS_TILE_ROWS")) e->tile_rows = std::min<uint32_t>(TILE_MAX_OWN_ROWS, std::max(1, atoi(v)));
   if (const char* v = getenv("CS_TILE_TARGET")) e->tile_target = std::min<uint32_t>(4 * TILE_THREADS, std::max(32, atoi(v)));
   const bool is_tile = cfg && (cfg->tile_cx1 | cfg->tile_cy1);
+  e->wide_ids = (e->flags & CS_CFG_WIDE_IDS) != 0;
+  if (e->wide_ids)
+    if (const char* v = getenv("CS_DEVICE_ID_LIMIT"))  // test knob: renumberings within a few hundred steps
+      e->id_limit = std::max<uint64_t>(4096u, std::min<uint64_t>((uint64_t)strtoull(v, nullptr, 10), CS_ID_LIMIT));
   if (e->set_geometry(is_tile, is_tile ? cfg->tile_cx0 : 0, is_tile ? cfg->tile_cx1 : 0, is_tile ? cfg->tile_cy0 : 0,
                       is_tile ? cfg->tile_cy1 : 0, is_tile ? cfg->halo_cells : 0) != 0)
     return create_failed(e, e->error);
@@ -205,6 +212,14 @@ cs_engine* cs_create(const cs_grid_desc* grid, const cs_device_cfg* cfg) {
   if (ok) hipMemset(e->ctr, 0, sizeof(Counters));
   if (const char* v = getenv("CS_FIRST_AGENT_ID")) {  // test knob: ids near the 31-bit limit without 2^31 agents
     e->next_id = std::min<uint64_t>((uint64_t)strtoull(v, nullptr, 10), CS_ID_LIMIT);
+    if (e->wide_ids) {  // the EXTERNAL counter, any u64; the device counter starts at 0 with its parity
+      e->ext_base = (uint64_t)strtoull(v, nullptr, 10);
+      e->dev_base = e->next_id = e->ext_base & 1u;
+      if (const char* w = getenv("CS_FIRST_DEVICE_ID")) {  // test knob: the device counter itself near its limit
+        const uint64_t d = std::min<uint64_t>((uint64_t)strtoull(w, nullptr, 10), e->id_limit - 2u);
+        e->dev_base = e->next_id = (d & ~1ull) | (e->ext_base & 1u);
+      }
+    }
     const uint32_t nid = (uint32_t)e->next_id;
     if (ok) hipMemcpy(&e->ctr->next_id, &nid, sizeof nid, hipMemcpyHostToDevice);
   }
@@ -297,14 +312,15 @@ int cs_remove_agent(cs_engine* e, uint64_t id) {
     }
   if (int rc = e->refresh_counts()) return rc;
   uint32_t found[2] = {0xFFFFFFFFu, 0u};
-  if (id < 0xFFFFFFFFull && e->n_slots) {
+  uint64_t dev = 0;  // (CS_CFG_WIDE_IDS: the external id's device id; otherwise the id itself)
+  if (e->dev_id(id, &dev) && dev < 0xFFFFFFFFull && e->n_slots) {
     if (!e->find_dev && hipMalloc(&e->find_dev, 2 * sizeof(uint32_t)) != hipSuccess) {
       e->error = "HIP error while removing an agent";
       return 90;
     }
     bool ok = hipMemcpyAsync(e->find_dev, found, sizeof found, hipMemcpyHostToDevice, e->stream) == hipSuccess;
     hipLaunchKernelGGL(k_remove_by_id, dim3((e->n_slots + 255u) / 256u), dim3(256), 0, e->stream, e->buf[e->cur],
-                       e->n_slots, e->ctr, e->gdev.tile, (uint32_t)id, e->find_dev);
+                       e->n_slots, e->ctr, e->gdev.tile, (uint32_t)dev, e->find_dev);
     ok = ok && hipMemcpyAsync(found, e->find_dev, sizeof found, hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
          hipStreamSynchronize(e->stream) == hipSuccess;
     if (!ok) {
@@ -341,6 +357,8 @@ uint64_t cs_kernel_stat(cs_engine* e, uint32_t which) {
   if (which == CS_STAT_EXCHANGES_AHEAD) return e->n_exchanges_ahead;
   if (which == CS_STAT_EXCHANGES_AHEAD_USED) return e->n_exchanges_ahead_used;
   if (which == CS_STAT_STEPS_ON_KEPT_WINDOWS) return e->n_steps_on_kept_windows;
+  if (which == CS_STAT_RENUMBERINGS) return e->n_renumberings;
+  if (which == CS_STAT_RENUMBER_NS) return e->renumber_ns;
   Counters c;
   if (e->read_counters(&c)) return 0;
   switch (which) {
@@ -444,7 +462,7 @@ size_t cs_read_agents(cs_engine* e, cs_agent_view* out, size_t cap) {
   size_t n = std::min(cap, live.size());
   for (size_t k = 0; k < n; ++k) {
     uint32_t i = live[k];
-    out[k].id = h.id[i];
+    out[k].id = e->ext_id(h.id[i]);
     e->to_global(h.cell[i], h.off[i].x, h.off[i].y, &out[k].x, &out[k].y);
     out[k].vx = h.vel[i].x;
     out[k].vy = h.vel[i].y;
@@ -648,7 +666,7 @@ int cs_query_radius_batch(cs_engine* e, size_t n, const double* xy, const double
     if (out_counts) out_counts[k] = counts[k];
     const size_t m = std::min<size_t>(counts[k], cap_per_query);
     for (size_t i = 0; i < m; ++i) {
-      out_ids[k * cap_per_query + i] = ids[k * cap_per_query + i];
+      out_ids[k * cap_per_query + i] = e->ext_id(ids[k * cap_per_query + i]);
       if (out_d2) out_d2[k * cap_per_query + i] = d2[k * cap_per_query + i];
       if (out_cells) out_cells[k * cap_per_query + i] = cells[k * cap_per_query + i];
     }
@@ -701,7 +719,7 @@ static int lp_callbacks_eval(cs_engine* e, const StepParams& P, const EpilogueCt
   };
   auto agent_of = [&](uint32_t i, double pvx, double pvy) {
     cs_lp_agent a;
-    a.agent_id = h.id[i];
+    a.agent_id = e->ext_id(h.id[i]);
     e->to_global(h.cell[i], h.off[i].x, h.off[i].y, &a.x, &a.y);
     a.vx = h.vel[i].x;
     a.vy = h.vel[i].y;
@@ -743,7 +761,7 @@ static int lp_callbacks_eval(cs_engine* e, const StepParams& P, const EpilogueCt
       for (uint32_t q = 0; q < counts[k]; ++q) {
         const uint32_t id = ids[k * cap + q];
         uint32_t slot = 0;
-        if (id == agents[k].agent_id || !find_slot(id, &slot)) continue;  // itself: lib.rs:284
+        if (id == h.id[slots[k]] || !find_slot(id, &slot)) continue;  // itself: lib.rs:284
         neighbours.push_back(agent_of(slot, 0.0, 0.0));
       }
       nb_begin[k + 1] = neighbours.size();
@@ -810,7 +828,7 @@ int cs_query_knn_batch(cs_engine* e, size_t n, const double* xy, size_t k, uint6
       }
       const size_t m = std::min(k, by_dist.size());
       for (size_t j = 0; j < m; ++j) {
-        out_ids[i * k + j] = by_dist[j].second;
+        out_ids[i * k + j] = e->ext_id(by_dist[j].second);
         if (out_d2) out_d2[i * k + j] = by_dist[j].first;
       }
       if (out_counts) out_counts[i] = m;
@@ -827,7 +845,7 @@ size_t cs_query_radius(cs_engine* e, double radius, double x, double y, uint64_t
   std::vector<uint32_t> ids;
   std::vector<float> d2;
   size_t cnt = radius_query(e, radius, x, y, &ids, &d2, cap, true);
-  for (size_t i = 0; i < ids.size() && i < cap; ++i) out_ids[i] = ids[i];
+  for (size_t i = 0; i < ids.size() && i < cap; ++i) out_ids[i] = e->ext_id(ids[i]);
   return cnt;
 }
 
@@ -857,7 +875,7 @@ size_t cs_query_knn(cs_engine* e, size_t k, double x, double y, uint64_t* out_id
     r *= 2.0;
   }
   size_t n = std::min(k, by_dist.size());
-  for (size_t i = 0; i < n; ++i) out_ids[i] = by_dist[i].second;
+  for (size_t i = 0; i < n; ++i) out_ids[i] = e->ext_id(by_dist[i].second);
   return n;
 }
 

@@ -229,7 +229,7 @@ struct cs_engine {
     if (n_slots)
       hipLaunchKernelGGL(k_snapshot, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, gdev, buf[cur],
                          n_slots, grid.offset_x, grid.offset_y, grid.cell_size, s.dev, (uint32_t)s.cap,
-                         s.count_dev);
+                         s.count_dev, ext_tab_dev[0], (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base);
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(s.gathered, stream));
     HIP_OK(hipStreamWaitEvent(copy_stream, s.gathered, 0));
@@ -362,6 +362,36 @@ struct cs_engine {
 
   uint64_t next_id = 0;  // last_alloc_agent_id, lib.rs:83 (host mirror; the device copy leads while
                          // source-sink steps run without a host sync)
+  // CS_CFG_WIDE_IDS: the ids the caller sees are 64-bit EXTERNAL ids; next_id and everything on the device count
+  // 32-bit device ids below id_limit, mapped by ext(d) = d < dev_base ? ext_of[d >> 1] : ext_base + (d - dev_base)
+  // (cs_kernels_ids.hip.inc).  When the counter would reach id_limit the live agents are renumbered in place
+  // (renumber_ids).  Without the flag the table stays empty and dev_base = ext_base = 0: ext(d) = d.
+  bool wide_ids = false;
+  uint64_t id_limit = CS_ID_LIMIT;  // device ids stay below it (CS_DEVICE_ID_LIMIT lowers it under the flag)
+  std::vector<uint64_t> ext_of;     // external ids of the agents alive at the last renumbering, ascending
+  uint64_t dev_base = 0, ext_base = 0;
+  uint64_t* ext_tab_dev[2] = {nullptr, nullptr};  // [0]: ext_of on the device (k_snapshot), [1]: the next one
+  size_t ext_tab_cap[2] = {0, 0};
+  uint32_t* ids_scratch = nullptr;  // the renumbering's sort: two key arrays, the digit histogram, the live count
+  size_t ids_scratch_words = 0;
+  uint64_t n_renumberings = 0;
+  uint64_t renumber_ns = 0;  // host wall time inside the renumberings (CS_STAT_RENUMBER_NS)
+  uint64_t ext_id(uint64_t d) const {
+    if (d < dev_base) return (d >> 1) < ext_of.size() ? ext_of[d >> 1] : UINT64_MAX;
+    return ext_base + (d - dev_base);
+  }
+  // the device id of external id x; false when no live agent can hold it
+  bool dev_id(uint64_t x, uint64_t* d) const {
+    if (x >= ext_base) {
+      if (x - ext_base >= 0xFFFFFFFFull) return false;
+      *d = dev_base + (x - ext_base);
+      return true;
+    }
+    const auto it = std::lower_bound(ext_of.begin(), ext_of.end(), x);
+    if (it == ext_of.end() || *it != x) return false;
+    *d = 2u * (uint64_t)(it - ext_of.begin()) + (x & 1u);
+    return true;
+  }
   bool counts_stale = false;   // steps ran fire-and-forget since the counters were last read
   bool errors_stale = false;   // ... steps of a plain crowd: counts cannot change, the error state can
   uint32_t async_steps = 0;
@@ -1252,7 +1282,7 @@ struct cs_engine {
       std::vector<uint8_t> some(m, 0);
       for (size_t k = 0; k < m; ++k) {
         uint32_t i = slots[k];
-        ids[k] = h.id[i];
+        ids[k] = ext_id(h.id[i]);
         to_global(h.cell[i], h.off[i].x, h.off[i].y, &pos[2 * k], &pos[2 * k + 1]);
         vel[2 * k] = h.vel[i].x;
         vel[2 * k + 1] = h.vel[i].y;
@@ -1268,6 +1298,198 @@ struct cs_engine {
     return 0;
   }
 
+  // ---- CS_CFG_WIDE_IDS: room for the next allocation ----
+  // n_new ids are about to be handed out, `in_flight` more may have been by steps still running on the device.  Without
+  // the flag the id space simply ends; with it the live agents are renumbered (renumber_ids), and only a crowd whose 2L
+  // device ids plus this allocation do not fit is refused.
+  int ids_room(uint64_t n_new, uint64_t in_flight) {
+    if (next_id + in_flight + n_new < id_limit) return 0;
+    if (!wide_ids) {
+      error = "agent id space exhausted (device ids are 31-bit)";
+      return 4;
+    }
+    if (int rc = refresh_counts()) return rc;  // the steps in flight
+    if (next_id + n_new < id_limit) return 0;
+    if (tile) {  // every tile of a mesh must agree on the new numbering: the mesh renumbers (mesh_ids_room) before this
+      error = "agent id space exhausted: a tile engine renumbers only through its mesh (cs_mesh_*)";
+      return 4;
+    }
+    const uint64_t live = n_alive_host;
+    if (2u * live + 1u + n_new >= id_limit) {
+      error = "agent id space exhausted: " + std::to_string(live) + " live agents need " + std::to_string(2u * live + 1u) +
+              " device ids after a renumbering, and this allocation " + std::to_string(n_new) +
+              " more; the device id limit is " + std::to_string(id_limit);
+      return 4;
+    }
+    return renumber_ids();
+  }
+
+  // Renumber the live agents in place: rank r (ascending device id) gets 2r + parity; ext_of becomes their external ids.
+  // Gather, radix sort and rewrite run on the device; the new table comes to the host once.
+  int renumber_ids() {
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_OK(hipStreamSynchronize(stream));
+    const uint32_t n = n_slots;
+    const size_t tiles_max = (n + IDS_TILE - 1u) / IDS_TILE;
+    const size_t words = 2u * (size_t)n + IDS_RADIX * tiles_max + 1u;
+    if (words > ids_scratch_words) {
+      hipFree(ids_scratch);
+      ids_scratch = nullptr;
+      ids_scratch_words = 0;
+      HIP_OK(hipMalloc(&ids_scratch, words * sizeof(uint32_t)));
+      ids_scratch_words = words;
+    }
+    uint32_t* keys = ids_scratch;
+    uint32_t* other = keys + n;
+    uint32_t* hist = other + n;
+    uint32_t* count_dev = hist + IDS_RADIX * tiles_max;
+    uint32_t n_live = 0;
+    if (n) {
+      HIP_OK(hipMemsetAsync(count_dev, 0, sizeof(uint32_t), stream));
+      hipLaunchKernelGGL(k_ids_gather, dim3((n + 255u) / 256u), dim3(256), 0, stream, buf[cur], n, keys, count_dev);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(&n_live, count_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      HIP_OK(hipStreamSynchronize(stream));
+    }
+    if (n_live > n) {
+      error = "renumbering agent ids: the live count exceeds the slots";
+      return 90;
+    }
+    if (n_live) {
+      const uint32_t tiles = (n_live + IDS_TILE - 1u) / IDS_TILE;
+      const uint32_t bits = next_id > 1 ? 64u - (uint32_t)__builtin_clzll(next_id - 1) : 1u;  // every id < next_id
+      for (uint32_t shift = 0; shift < bits; shift += 4u) {
+        hipLaunchKernelGGL(k_ids_hist, dim3(tiles), dim3(IDS_BLOCK), 0, stream, keys, n_live, shift, hist, tiles);
+        hipLaunchKernelGGL(k_ids_scan, dim3(1), dim3(IDS_BLOCK), 0, stream, hist, IDS_RADIX * tiles);
+        hipLaunchKernelGGL(k_ids_scatter, dim3(tiles), dim3(IDS_BLOCK), 0, stream, keys, other, n_live, shift, hist, tiles);
+        std::swap(keys, other);
+      }
+      if (ext_tab_cap[1] < n_live) {
+        hipFree(ext_tab_dev[1]);
+        ext_tab_dev[1] = nullptr;
+        ext_tab_cap[1] = 0;
+        HIP_OK(hipMalloc(&ext_tab_dev[1], (size_t)n_live * sizeof(uint64_t)));
+        ext_tab_cap[1] = n_live;
+      }
+      hipLaunchKernelGGL(k_ids_renumber, dim3((n + 255u) / 256u), dim3(256), 0, stream, buf[cur], n, keys, n_live);
+      hipLaunchKernelGGL(k_ids_table, dim3((n_live + 255u) / 256u), dim3(256), 0, stream, keys, n_live, ext_tab_dev[0],
+                         (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base, ext_tab_dev[1]);
+      HIP_OK(hipGetLastError());
+    }
+    std::vector<uint64_t> tab(n_live);
+    if (n_live)
+      HIP_OK(hipMemcpyAsync(tab.data(), ext_tab_dev[1], (size_t)n_live * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    const uint64_t next_ext = ext_id(next_id);  // what the next allocation would have been called
+    ext_of.swap(tab);
+    std::swap(ext_tab_dev[0], ext_tab_dev[1]);
+    std::swap(ext_tab_cap[0], ext_tab_cap[1]);
+    ext_base = next_ext;
+    dev_base = 2u * (uint64_t)n_live + ((2u * (uint64_t)n_live ^ ext_base) & 1u);
+    next_id = dev_base;
+    const uint32_t nid = (uint32_t)next_id;
+    HIP_OK(hipMemcpy(&ctr->next_id, &nid, sizeof nid, hipMemcpyHostToDevice));
+    halo_invalidate();
+    ++n_renumberings;
+    renumber_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+  }
+
+  // ---- a mesh's renumbering, in two halves around the gather of the mesh (cs_mesh.hip.inc: mesh_ids_room) ----
+  // 1. this tile's live agents' external ids, ascending (no ghosts may be present: between two mesh steps a tile holds
+  //    exactly the agents it stepped, each agent is held by one tile)
+  // the device counter, exactly (a tile hands out ids on the device without the host: cs_spawn_commit_dev)
+  int sync_next_id() {
+    if (int rc = refresh_counts()) return rc;
+    if (aux_stream) HIP_OK(hipStreamSynchronize(aux_stream));  // (an exchange made ahead)
+    Counters c;
+    if (int rc = read_counters(&c)) return rc;
+    next_id = c.next_id;
+    return 0;
+  }
+  int wide_owned_ext(std::vector<uint64_t>* out) {
+    if (int rc = sync_next_id()) return rc;
+    if (ghosts_present) {
+      error = "renumbering agent ids: the tile holds ghosts (only between two mesh steps)";
+      return 90;
+    }
+    const uint32_t n = n_slots;
+    const size_t tiles_max = (n + IDS_TILE - 1u) / IDS_TILE;
+    const size_t words = 2u * (size_t)n + IDS_RADIX * tiles_max + 1u;
+    if (words > ids_scratch_words) {
+      hipFree(ids_scratch);
+      ids_scratch = nullptr;
+      ids_scratch_words = 0;
+      HIP_OK(hipMalloc(&ids_scratch, words * sizeof(uint32_t)));
+      ids_scratch_words = words;
+    }
+    uint32_t* keys = ids_scratch;
+    uint32_t* other = keys + n;
+    uint32_t* hist = other + n;
+    uint32_t* count_dev = hist + IDS_RADIX * tiles_max;
+    uint32_t n_live = 0;
+    if (n) {
+      HIP_OK(hipMemsetAsync(count_dev, 0, sizeof(uint32_t), stream));
+      hipLaunchKernelGGL(k_ids_gather, dim3((n + 255u) / 256u), dim3(256), 0, stream, buf[cur], n, keys, count_dev);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(&n_live, count_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      HIP_OK(hipStreamSynchronize(stream));
+    }
+    if (n_live > n) {
+      error = "renumbering agent ids: the live count exceeds the slots";
+      return 90;
+    }
+    out->assign(n_live, 0);
+    if (!n_live) return 0;
+    const uint32_t tiles = (n_live + IDS_TILE - 1u) / IDS_TILE;
+    const uint32_t bits = next_id > 1 ? 64u - (uint32_t)__builtin_clzll(next_id - 1) : 1u;
+    for (uint32_t shift = 0; shift < bits; shift += 4u) {
+      hipLaunchKernelGGL(k_ids_hist, dim3(tiles), dim3(IDS_BLOCK), 0, stream, keys, n_live, shift, hist, tiles);
+      hipLaunchKernelGGL(k_ids_scan, dim3(1), dim3(IDS_BLOCK), 0, stream, hist, IDS_RADIX * tiles);
+      hipLaunchKernelGGL(k_ids_scatter, dim3(tiles), dim3(IDS_BLOCK), 0, stream, keys, other, n_live, shift, hist, tiles);
+      std::swap(keys, other);
+    }
+    if (int rc = ext_tab_reserve(1, n_live)) return rc;
+    hipLaunchKernelGGL(k_ids_table, dim3((n_live + 255u) / 256u), dim3(256), 0, stream, keys, n_live, ext_tab_dev[0],
+                       (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base, ext_tab_dev[1]);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(out->data(), ext_tab_dev[1], (size_t)n_live * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+  }
+  // 2. the mesh-wide table (ascending external ids of every live agent of the mesh, the same on every tile): every live
+  //    agent here takes 2 * (its rank in it) + parity; new ids continue from 2L with the parity of next_ext
+  int wide_apply_table(const std::vector<uint64_t>& all, uint64_t next_ext) {
+    const uint32_t L = (uint32_t)all.size();
+    if (int rc = ext_tab_reserve(1, L)) return rc;
+    if (L) HIP_OK(hipMemcpyAsync(ext_tab_dev[1], all.data(), (size_t)L * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    if (n_slots && L)
+      hipLaunchKernelGGL(k_ids_renumber_ext, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, buf[cur], n_slots,
+                         ext_tab_dev[0], (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base, ext_tab_dev[1], L);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(stream));
+    ext_of = all;
+    std::swap(ext_tab_dev[0], ext_tab_dev[1]);
+    std::swap(ext_tab_cap[0], ext_tab_cap[1]);
+    ext_base = next_ext;
+    dev_base = 2u * (uint64_t)L + ((2u * (uint64_t)L ^ ext_base) & 1u);
+    next_id = dev_base;
+    const uint32_t nid = (uint32_t)next_id;
+    HIP_OK(hipMemcpy(&ctr->next_id, &nid, sizeof nid, hipMemcpyHostToDevice));
+    halo_invalidate();
+    ++n_renumberings;
+    return 0;
+  }
+  int ext_tab_reserve(int k, uint32_t n) {
+    if (ext_tab_cap[k] >= n) return 0;
+    hipFree(ext_tab_dev[k]);
+    ext_tab_dev[k] = nullptr;
+    ext_tab_cap[k] = 0;
+    HIP_OK(hipMalloc(&ext_tab_dev[k], (size_t)std::max<uint32_t>(n, 1u) * sizeof(uint64_t)));
+    ext_tab_cap[k] = std::max<uint32_t>(n, 1u);
+    return 0;
+  }
+
   // ---- Simulation::add_agents, lib.rs:119-156 ----
   int add_agents(const double* xy, size_t n, uint32_t group, uint32_t owner, uint64_t* out_ids) {
     halo_invalidate();  // on every tile alike, whether or not it keeps any of them (exchange made ahead)
@@ -1275,10 +1497,7 @@ struct cs_engine {
     last_failed_add_index = SIZE_MAX;
     if (n == 0) return 0;
     if (int rc = refresh_counts()) return rc;
-    if (next_id + n >= CS_ID_LIMIT) {
-      error = "agent id space exhausted (device ids are 31-bit)";
-      return 4;
-    }
+    if (int rc = ids_room(n, 0)) return rc;
     if (int rc = reserve((uint64_t)n_slots + n)) return rc;
     std::vector<float2> off, vel;
     std::vector<uint32_t> ids, cells, meta;
@@ -1287,7 +1506,8 @@ struct cs_engine {
     for (size_t k = 0; k < n; ++k) {
       uint32_t c;
       float ox, oy;
-      uint64_t id = next_id++;  // consumed even when the insert fails (lib.rs:128-129)
+      const uint64_t dev = next_id++;  // consumed even when the insert fails (lib.rs:128-129)
+      const uint64_t id = ext_id(dev);
       int where = to_cell(xy[2 * k], xy[2 * k + 1], &c, &ox, &oy);
       if (where == 1) {
         // The reference has already put the agent into `agents` when the index insert
@@ -1302,7 +1522,7 @@ struct cs_engine {
       if (out_ids) out_ids[k] = id;
       if (where == 2) continue;  // another tile owns it
       off.push_back(make_float2(ox, oy));
-      ids.push_back((uint32_t)id);
+      ids.push_back((uint32_t)dev);
       cells.push_back(c);
       cs_event ev;
       ev.kind = CS_EVENT_SPAWNED;
@@ -1414,13 +1634,13 @@ struct cs_engine {
       float ox, oy;
       if (to_cell(sinks[s].d.source_x, sinks[s].d.source_y, &c, &ox, &oy) != 0) {
         // another tile's spawn inside my ring: a ghost for this step (see SinkDev.ghost_cell)
-        if (my_id < CS_ID_LIMIT && to_ring_cell(sinks[s].d.source_x, sinks[s].d.source_y, &c, &ox, &oy)) {
+        if (my_id < id_limit && to_ring_cell(sinks[s].d.source_x, sinks[s].d.source_y, &c, &ox, &oy)) {
           mine.push_back(SpawnRecord{ox, oy, (uint32_t)my_id, c, sinks[s].group, sinks[s].spawn_route});
           ++n_ghost_spawns;
         }
         continue;
       }
-      if (my_id >= CS_ID_LIMIT) {
+      if (my_id >= id_limit) {
         error = "agent id space exhausted (device ids are 31-bit)";
         return 4;
       }
@@ -1429,14 +1649,14 @@ struct cs_engine {
         cs_event ev;
         ev.kind = CS_EVENT_SPAWNED;
         ev.source_sink = (uint32_t)s;
-        ev.id = my_id;
+        ev.id = ext_id(my_id);
         ev.x = sinks[s].d.source_x;
         ev.y = sinks[s].d.source_y;
         events.push_back(ev);
       }
       const cs_hlp_desc& p = hlps[sinks[s].d.hlp];
       if (p.kind == CS_HLP_CALLBACK && p.set_target && !sinks[s].waypoints.empty())
-        p.set_target(p.user, my_id, sinks[s].d.source_x, sinks[s].d.source_y, sinks[s].waypoints[0],
+        p.set_target(p.user, ext_id(my_id), sinks[s].d.source_x, sinks[s].d.source_y, sinks[s].waypoints[0],
                      sinks[s].waypoints[1], sinks[s].d.radius_sink, sinks[s].d.radius_sink);
     }
     next_id = id;
@@ -1498,7 +1718,7 @@ struct cs_engine {
     spawn_on_device = true;
     committed_spawns = 0;
     if (!ns || !pending_want) return 0;
-    if (next_id + (uint64_t)(async_steps + 1) * ns >= CS_ID_LIMIT) {
+    if (next_id + (uint64_t)(async_steps + 1) * ns >= id_limit) {
       error = "agent id space exhausted (device ids are 31-bit)";
       return 4;
     }
@@ -1563,10 +1783,7 @@ struct cs_engine {
       want_ring = (want_ring + 1) % kWantRing;  // a slot is reused only after a host sync
       n_want = eval_generators(dt_seconds, want);
       if (n_want) {
-        if (next_id + async_steps * sinks.size() + n_want >= CS_ID_LIMIT) {
-          error = "agent id space exhausted (device ids are 31-bit)";
-          return 4;
-        }
+        if (int rc = ids_room(n_want, (uint64_t)async_steps * sinks.size())) return rc;
         if (int rc = reserve((uint64_t)n_slots + n_want)) return rc;
         if (int rc = mark_occupancy()) return rc;  // no-op right after a step
         if (int rc = recount()) return rc;         // no-op right after a step
@@ -2110,7 +2327,7 @@ struct cs_engine {
       cs_event ev;
       ev.kind = CS_EVENT_SPAWNED;
       ev.source_sink = slots[k];
-      ev.id = first_id + k;
+      ev.id = ext_id(first_id + k);
       ev.x = h.d.source_x;
       ev.y = h.d.source_y;
       if (record_events) events.push_back(ev);
@@ -2152,10 +2369,10 @@ struct cs_engine {
         double px, py;
         to_global(ev.cell, ev.ox, ev.oy, &px, &py);
         if (cb)
-          p.set_target(p.user, ev.id, px, py, h.waypoints[2 * ev.next_wp], h.waypoints[2 * ev.next_wp + 1],
+          p.set_target(p.user, ext_id(ev.id), px, py, h.waypoints[2 * ev.next_wp], h.waypoints[2 * ev.next_wp + 1],
                        h.d.radius_sink, h.d.radius_sink);
         else if (tile)
-          route_misses.push_back(cs_route_miss{ev.id, g.hlp, ev.slot, px, py, h.waypoints[2 * ev.next_wp],
+          route_misses.push_back(cs_route_miss{ext_id(ev.id), g.hlp, ev.slot, px, py, h.waypoints[2 * ev.next_wp],
                                                h.waypoints[2 * ev.next_wp + 1]});
         else
           route_set_target(g.hlp, ev.slot, px, py, h.waypoints[2 * ev.next_wp], h.waypoints[2 * ev.next_wp + 1]);
@@ -2169,11 +2386,12 @@ struct cs_engine {
       for (auto& it : d) {
         const HostGroup& g = groups[meta_group(gdev, it.y)];
         const cs_hlp_desc& p = hlps[g.hlp];
-        if (p.kind == CS_HLP_CALLBACK && p.remove_agent) p.remove_agent(p.user, it.x);
+        const uint64_t id = ext_id(it.x);
+        if (p.kind == CS_HLP_CALLBACK && p.remove_agent) p.remove_agent(p.user, id);
         cs_event ev;
         ev.kind = CS_EVENT_DESTROYED;
         ev.source_sink = g.sink >= 0 ? (uint32_t)g.sink : UINT32_MAX;
-        ev.id = it.x;
+        ev.id = id;
         ev.x = ev.y = 0;
         if (record_events) events.push_back(ev);
       }
@@ -2440,7 +2658,7 @@ struct cs_engine {
     }
     if (n == 0) return 0;
     for (size_t k = 0; k < n; ++k)  // (host memory: records somebody else made; the kernels read the right of way
-      if (rec[k].id >= CS_ID_LIMIT) {  //  from the sign of an id difference, which needs ids below 2^31)
+      if (rec[k].id >= id_limit) {  //  from the sign of an id difference, which needs ids below 2^31)
         error = "cs_tile_import: a record's agent id is beyond the device's 31-bit id space";
         return 3;
       }

@@ -559,7 +559,8 @@ __global__ void k_route_assign(uint32_t* __restrict__ route, uint32_t n_slots, c
 // Streaming agents view: live agents of the current state, global f64 positions, compacted in
 // no particular order (one atomic per wave).
 __global__ void k_snapshot(GridDev g, AgentArrays a, uint32_t n, double off_x, double off_y, double cell_size,
-                           cs_snapshot_record* __restrict__ out, uint32_t cap, uint32_t* __restrict__ count) {
+                           cs_snapshot_record* __restrict__ out, uint32_t cap, uint32_t* __restrict__ count,
+                           const uint64_t* __restrict__ ext_tab, uint32_t n_tab, uint32_t dev_base, uint64_t ext_base) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t cell = i < n ? a.cell[i] : CS_INVALID_CELL;
   const bool live = cell != CS_INVALID_CELL;
@@ -579,7 +580,7 @@ __global__ void k_snapshot(GridDev g, AgentArrays a, uint32_t n, double off_x, d
   r.y = off_y + ((double)(g.org_y + cy) * cell_size + (double)o.y);
   r.vx = v.x;
   r.vy = v.y;
-  r.id = a.id[i];
+  r.id = (uint32_t)ext_id_dev(a.id[i], ext_tab, n_tab, dev_base, ext_base);  // CS_CFG_WIDE_IDS: the low 32 bits
   r.next_waypoint = meta_waypoint(g, a.meta[i]);
   out[k] = r;
 }

@@ -49,6 +49,9 @@ struct cs_mesh {
     uint32_t hlp;
   };
   std::vector<Limbo> limbo;
+  // CS_CFG_WIDE_IDS: an upper bound of the device ids the tiles have handed out, moved by the same calls on every rank
+  // (adds, and one id per source-sink slot and step), so that every rank decides alike when to renumber (mesh_ids_room)
+  uint64_t id_bound = 0;
   // A step that failed on ANY tile ends the run of the whole mesh: the tiles before the failing one have taken the
   // step, the ones behind it have not, and the next exchange would mix two time steps.  Every later call fails with
   // the first error, on every rank alike (the single engine commits nothing on "Index out of bounds", lib.rs:299-302
@@ -259,6 +262,83 @@ static int mesh_host_gatherv(cs_mesh* m, const void* mine, size_t bytes, std::ve
   for (size_t r = 0; r < nr; ++r) out[r].assign(all.begin() + r * most, all.begin() + r * most + sizes[r]);
   return 0;
 }
+// CS_CFG_WIDE_IDS: room for n_new more device ids.  While the rank-uniform bound allows, nothing happens; else every
+// tile synchronises, and if the exact counter needs it the mesh renumbers: each tile sorts its live agents' external ids
+// on the device, the mesh gathers them (counts, then ids: mesh_host_gatherv over the host transport or RCCL; the tiles of
+// this process directly), every rank merges the same global table, and each tile maps its agents by binary search in it
+// (k_ids_renumber_ext).  Between two mesh steps no tile holds ghosts, and what the step kernels packed is voided, so the
+// next exchange carries the new ids.  Collective: every rank makes the same calls.
+// merge the ascending runs of v ending at `ends` (pairwise, in place)
+static void mesh_merge_runs(std::vector<uint64_t>& v, std::vector<size_t> ends) {
+  while (ends.size() > 1) {
+    std::vector<size_t> next;
+    for (size_t i = 0; i < ends.size(); i += 2) {
+      if (i + 1 < ends.size()) {
+        const size_t b = i ? ends[i - 1] : 0;
+        std::inplace_merge(v.begin() + (long)b, v.begin() + (long)ends[i], v.begin() + (long)ends[i + 1]);
+      }
+      next.push_back(ends[std::min(i + 1, ends.size() - 1)]);
+    }
+    ends.swap(next);
+  }
+}
+static int mesh_ids_room(cs_mesh* m, uint64_t n_new) {
+  if (!(m->flags & CS_CFG_WIDE_IDS) || m->tiles.empty()) return 0;
+  cs_engine* t0 = m->tiles[0];
+  if (m->id_bound + n_new < t0->id_limit) {
+    m->id_bound += n_new;
+    return 0;
+  }
+  const auto t_start = std::chrono::steady_clock::now();
+  for (cs_engine* e : m->tiles) {
+    hipSetDevice(e->device);
+    if (int rc = e->sync_next_id()) return m->fail(e, rc);
+  }
+  if (t0->next_id + n_new < t0->id_limit) {  // the bound was loose: no renumbering yet
+    m->id_bound = t0->next_id + n_new;
+    return 0;
+  }
+  std::vector<uint64_t> all, mine;
+  std::vector<size_t> ends;
+  for (cs_engine* e : m->tiles) {
+    hipSetDevice(e->device);
+    if (int rc = e->wide_owned_ext(&mine)) return m->fail(e, rc);
+    all.insert(all.end(), mine.begin(), mine.end());
+    ends.push_back(all.size());
+  }
+  mesh_merge_runs(all, ends);  // every tile's list is sorted on its device
+  if (m->distributed) {
+    std::vector<std::vector<unsigned char>> parts;
+    if (int rc = mesh_host_gatherv(m, all.data(), all.size() * sizeof(uint64_t), parts)) return rc;
+    all.clear();
+    ends.clear();
+    for (const auto& p : parts) {
+      const size_t k = p.size() / sizeof(uint64_t), at = all.size();
+      all.resize(at + k);
+      if (k) std::memcpy(all.data() + at, p.data(), k * sizeof(uint64_t));
+      ends.push_back(all.size());
+    }
+    mesh_merge_runs(all, ends);  // (every rank's part is sorted)
+  }
+  const uint64_t live = all.size();
+  if (2u * live + 1u + n_new >= t0->id_limit) {
+    m->error = "agent id space exhausted: " + std::to_string(live) + " live agents need " + std::to_string(2u * live + 1u) +
+               " device ids after a renumbering, and this allocation " + std::to_string(n_new) +
+               " more; the device id limit is " + std::to_string(t0->id_limit);
+    return 4;
+  }
+  const uint64_t next_ext = t0->ext_id(t0->next_id);
+  for (cs_engine* e : m->tiles) {
+    hipSetDevice(e->device);
+    if (int rc = e->wide_apply_table(all, next_ext)) return m->fail(e, rc);
+  }
+  const uint64_t ns = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() -
+                                                                                      t_start).count();
+  for (cs_engine* e : m->tiles) e->renumber_ns += ns;
+  m->id_bound = t0->next_id + n_new;
+  return 0;
+}
+
 // pinned staging for the halo buffers of the local tile (after mesh_set_buffers)
 static int mesh_host_stage_alloc(cs_mesh* m) {
   for (int d = 0; d < 8; ++d) {
@@ -538,6 +618,7 @@ cs_mesh* cs_mesh_create(const cs_grid_desc* grid, const cs_mesh_desc* d) {
                     "(every rank passes the same cs_grid_desc and cs_mesh_desc but for `rank` and the device)");
   }
   if (hipStreamSynchronize(m->stream) != hipSuccess) return bad(m, "cs_mesh_create: HIP error");
+  m->id_bound = m->tiles.empty() ? 0 : m->tiles[0]->next_id;
   return m;
 }
 
@@ -598,6 +679,7 @@ int cs_mesh_add_agents(cs_mesh* m, const double* xy, size_t n, uint32_t hlp, uin
   // EVERY tile takes the call, also when it fails: the agents before the failing one stay added (lib.rs:146-149) and
   // every tile's id counter moves alike (the loop used to leave at the first tile that reported the failure: the tiles
   // behind it missed the agents before the failing one)
+  if (int rc = mesh_ids_room(m, n)) return rc;
   int first = 0;
   cs_engine* failed = nullptr;
   for (cs_engine* e : m->tiles)
@@ -773,6 +855,8 @@ int cs_mesh_step(cs_mesh* m, double dt, cs_step_report* report) {
     m->error = "Index out of bounds";
     return 1;
   }
+  if (m->flags & CS_CFG_WIDE_IDS)  // (at most one spawn per source-sink slot and step)
+    if (int rc = mesh_ids_room(m, m->has_sinks ? (uint64_t)cs_source_sink_slots(m->tiles[0]) : 0u)) return rc;
   auto add = [&](const cs_step_report& r) {
     if (!report) return;
     report->n_agents += r.n_agents; report->n_spawned += r.n_spawned; report->n_destroyed += r.n_destroyed;

@@ -18,11 +18,14 @@ pub const CS_CFG_FORCE_GATHER: u32 = 1;
 pub const CS_CFG_FORCE_TILED: u32 = 2;
 pub const CS_CFG_DENSE: u32 = 4;
 pub const CS_CFG_TILE_OVERLAP: u32 = 8;
+pub const CS_CFG_WIDE_IDS: u32 = 16;
 pub const CS_STAT_WINDOWS_OFF_LDS: u32 = 0;
 pub const CS_STAT_WINDOWS_CHUNKED: u32 = 1;
 pub const CS_STAT_EXCHANGES_AHEAD: u32 = 2;
 pub const CS_STAT_EXCHANGES_AHEAD_USED: u32 = 3;
 pub const CS_STAT_STEPS_ON_KEPT_WINDOWS: u32 = 4;
+pub const CS_STAT_RENUMBERINGS: u32 = 5;
+pub const CS_STAT_RENUMBER_NS: u32 = 6;
 
 pub const CS_HLP_NONE: u32 = 0;
 pub const CS_HLP_CONSTANT: u32 = 1;

@@ -1,0 +1,252 @@
+"""CS_CFG_WIDE_IDS: 64-bit external agent ids over the engine's 32-bit device ids.
+
+Without the flag the device ids end at 2^31 ("agent id space exhausted", test_gpu_parity.py::
+test_ids_up_to_the_31_bit_limit).  With it the ids the caller sees are external u64 ids, and the engine renumbers the
+live agents' device ids in place when they run out (order and parity kept).  Two test knobs make that reachable in a few
+hundred steps: CS_FIRST_AGENT_ID sets the external counter (any u64), CS_DEVICE_ID_LIMIT lowers the device limit
+(floor 4096).  The oracle numbers its agents from 0, so its ids are compared with the engine's minus the first id."""
+import numpy as np
+import pytest
+
+from oracle_sim import OracleSimulation
+from rmf_crowdsim_amd import (CS_CFG_WIDE_IDS, CrowdSimError, EventListener, HighLevelPlanner, IdParityHighLevelPlan,
+                              LocalPlanner, LocationHash2D, MonotonicCrowd, NoLocalPlan, Simulation, SourceSink,
+                              StubHighLevelPlan, Zanlungo, _abi, scenes)
+
+pytestmark = pytest.mark.gpu
+
+FLAGS = pytest.mark.parametrize("flags", [2, 1], ids=["tiled", "gather"])
+
+
+def test_wide_ids_go_past_the_31_bit_limit(monkeypatch):
+    """The add that test_ids_up_to_the_31_bit_limit sees refused succeeds under the flag and returns id 2^31 - 2, and
+    the crowd moves bit for bit like the same crowd with ids from 0 and no flag."""
+    n = 6000
+    pts, grid, extent, group = scenes.uniform_crowd(n, seed=5, cell_size=2.0)
+    for flags in (2, 1):
+        runs = []
+        for first, wide in ((0, 0), (2 ** 31 - 2 - n, CS_CFG_WIDE_IDS)):
+            if first:
+                monkeypatch.setenv("CS_FIRST_AGENT_ID", str(first))
+            else:
+                monkeypatch.delenv("CS_FIRST_AGENT_ID", raising=False)
+            sim = Simulation(LocationHash2D(**grid), flags=flags | wide)
+            ids = scenes.add_counterflow(sim, pts, group, scenes.CREEP_SPEED, Zanlungo(*scenes.METRIC_ZANLUNGO), 2.0)
+            assert sorted(int(i) for i in ids) == list(range(first, first + n))
+            for _ in range(20):
+                sim.step(0.05, report=False)
+            extra = sim.add_agents([(extent / 2 + 0.31, extent / 2 + 0.27)], StubHighLevelPlan((0.0, 0.0)),
+                                   NoLocalPlan(), 1.0)
+            assert extra == [first + n]
+            for _ in range(20):
+                sim.step(0.05, report=False)
+            a = sim.read_agents()
+            assert (a["id"] == np.arange(first, first + n + 1)).all()
+            runs.append(a)
+            sim.close()
+        assert runs[1][-1]["id"] == 2 ** 31 - 2
+        for field in ("x", "y", "vx", "vy", "next_waypoint"):
+            assert runs[0][field].tobytes() == runs[1][field].tobytes(), (flags, field)
+        assert np.abs(runs[0]["vx"]).max() > 0.0
+
+
+# ---- a scene that goes through several renumberings, engine against the oracle ----------------------------------
+class TargetPlan(HighLevelPlanner):
+    """Walks towards the last target set_target gave it; logs the ids it is told about."""
+
+    def __init__(self, shift):
+        self.shift, self.targets, self.log = shift, {}, []
+
+    def get_desired_velocity(self, agent, time):
+        t = self.targets.get(agent.agent_id)
+        if t is None:
+            return None
+        d = t - agent.position
+        return tuple(1.3 * d / max(np.linalg.norm(d), 1e-9))
+
+    def set_target(self, agent, point, tolerance):
+        self.targets[agent.agent_id] = np.array(point)
+        self.log.append(("set", agent.agent_id - self.shift, tuple(point)))
+
+    def remove_agent_id(self, agent_id):
+        self.targets.pop(agent_id, None)
+        self.log.append(("remove", agent_id - self.shift))
+
+
+class LoggingPlanner(LocalPlanner):
+    """A host local planner: keeps the recommended velocity, logs the ids of the agent and its neighbours."""
+
+    def __init__(self, shift):
+        self.shift, self.log = shift, []
+
+    def get_desired_velocity(self, agent, nearby_agents, recommended_velocity):
+        self.log.append((agent.agent_id - self.shift, tuple(a.agent_id - self.shift for a in nearby_agents)))
+        return float(recommended_velocity[0]), float(recommended_velocity[1])
+
+
+class Recorder(EventListener):
+    def __init__(self, shift):
+        self.shift, self.events = shift, []
+
+    def agent_spawned(self, position, agent):
+        self.events.append(("spawned", agent - self.shift))
+
+    def agent_destroyed(self, agent):
+        self.events.append(("destroyed", agent - self.shift))
+
+
+STEPS, CHURN = 140, 250
+
+
+def _renumbering_scene(sim, shift, steps=STEPS):
+    """~600 agents in contact with an id-parity planner, 16 agents of a host local planner, looping and one-way
+    source-sinks (TargetPlan: set_target / remove callbacks) and CHURN parked agents added and removed again (by id)
+    every step: ~36,000 ids in all.  Returns what has to equal the oracle's, with ids shifted by `shift`."""
+    rec = Recorder(shift)
+    sim.add_event_listener(rec)
+    zan = Zanlungo(*scenes.METRIC_ZANLUNGO)
+    crowd = scenes.jittered_lattice(600, 0.6, (50.0, 30.0), 0.2, 11, columns=30)
+    sim.add_agents(crowd, IdParityHighLevelPlan((0.0, 0.02)), zan, 2.0)
+    lp = LoggingPlanner(shift)
+    sim.add_agents(scenes.jittered_lattice(16, 0.8, (30.0, 50.0), 0.2, 12, columns=4), IdParityHighLevelPlan((0.05, 0.0)),
+                   lp, 2.0)
+    plan = TargetPlan(shift)
+    for k in range(12):  # loop_forever: these agents live on, through every renumbering
+        y = 10.0 + 3.0 * k
+        sim.add_source_sink(SourceSink((10.0, y), 0.5, MonotonicCrowd(20.0), plan, NoLocalPlan(), [(16.0, y), (10.0, y)],
+                                       True, 2.0))
+    for k in range(8):  # one way: destroyed at the sink
+        y = 60.0 + 3.0 * k
+        sim.add_source_sink(SourceSink((80.0, y), 0.5, MonotonicCrowd(20.0), StubHighLevelPlan((-1.3, 0.0)), zan,
+                                       [(74.0, y)], False, 2.0))
+    rng = np.random.default_rng(3)
+    parked = StubHighLevelPlan((0.0, 0.0))
+    last, per_step, queries = [], [], []
+    for s in range(steps):
+        spots = np.stack([rng.uniform(2.0, 20.0, CHURN), rng.uniform(70.0, 96.0, CHURN)], axis=1)
+        now = sim.add_agents(spots, parked, NoLocalPlan(), 1.0)
+        for i in last:
+            sim.remove_agents(i)
+        last = now
+        sim.step(0.05)
+        per_step.append((len(sim), sim.last_report["n_spawned"], sim.last_report["n_destroyed"]))
+        if s % 5 == 4:  # the ids between the renumberings too (every ~25 steps here)
+            per_step.append([int(i) - shift for i in sim.read_agents()["id"]])
+        if s % 35 == 34:
+            queries.append((sorted(i - shift for i in sim.get_neighbours_in_radius(3.0, (55.0, 35.0))),
+                            [i - shift for i in sim.get_nearest_neighbours(6, (31.0, 51.0))],
+                            [[i - shift for i in q] for q in sim.query_radius_batch([2.0, 4.0], [(12.0, 20.0),
+                                                                                                (53.0, 33.0)])],
+                            [[i - shift for i in q] for q in sim.query_knn_batch(4, [(60.0, 36.0)])]))
+    tail = sim.add_agents([(3.0, 3.0)], parked, NoLocalPlan(), 1.0)[0] - shift
+    a = sim.read_agents()
+    return dict(per_step=per_step, events=rec.events, plan=plan.log, lp=lp.log, queries=queries, tail=tail,
+                agents=a, ids=a["id"] - np.uint64(shift))
+
+
+_oracle_cache = {}
+
+
+def _oracle_run():
+    if "r" not in _oracle_cache:
+        ora = OracleSimulation(LocationHash2D(100.0, 100.0, 2.0, (0.0, 0.0)))
+        _oracle_cache["r"] = _renumbering_scene(ora, 0)
+        ora.close()
+    return _oracle_cache["r"]
+
+
+@FLAGS
+def test_renumberings_match_the_oracle(flags, monkeypatch):
+    first = 2 ** 32 - 1000  # even: the external ids cross 2^32 on the way
+    monkeypatch.setenv("CS_FIRST_AGENT_ID", str(first))
+    monkeypatch.setenv("CS_DEVICE_ID_LIMIT", "8192")
+    sim = Simulation(LocationHash2D(100.0, 100.0, 2.0, (0.0, 0.0)), flags=flags | CS_CFG_WIDE_IDS)
+    got = _renumbering_scene(sim, first)
+    assert sim.kernel_stat(_abi.CS_STAT_RENUMBERINGS) >= 3 and sim.kernel_stat(_abi.CS_STAT_RENUMBER_NS) > 0
+    sim.close()
+    want = _oracle_run()
+    # an epoch hands out at most 8192 device ids: more than 4 * 8192 ids took at least three renumberings
+    assert got["tail"] == want["tail"] and got["tail"] > 4 * 8192
+    assert got["per_step"] == want["per_step"]
+    assert got["events"] == want["events"]
+    assert got["plan"] == want["plan"] and len(got["plan"]) > 100
+    assert got["lp"] == want["lp"] and any(len(nb) for _, nb in got["lp"])
+    # radius queries (single and batch) and the single k-NN against the oracle; the batch k-NN differs from the
+    # oracle's with or without the flag, so it is held to the same engine without the flag and with ids from 0
+    assert [q[:3] for q in got["queries"]] == [q[:3] for q in want["queries"]]
+    assert all(len(q[0]) for q in got["queries"])
+    monkeypatch.delenv("CS_FIRST_AGENT_ID")
+    monkeypatch.delenv("CS_DEVICE_ID_LIMIT")
+    plain = Simulation(LocationHash2D(100.0, 100.0, 2.0, (0.0, 0.0)), flags=flags)
+    base = _renumbering_scene(plain, 0)
+    plain.close()
+    assert got["queries"] == base["queries"] and got["events"] == base["events"]
+    for field in ("x", "y", "vx", "vy", "next_waypoint"):
+        assert got["agents"][field].tobytes() == base["agents"][field].tobytes(), field
+    a, b = got["agents"], want["agents"]
+    assert (got["ids"] == b["id"]).all()
+    dp = np.hypot(a["x"] - b["x"], a["y"] - b["y"])
+    assert float(dp.max() / 100.0) <= 1e-4
+    assert (a["next_waypoint"] == b["next_waypoint"]).all()
+
+
+@FLAGS
+def test_ids_beyond_2_to_the_32(flags, monkeypatch):
+    """Ids from 2^40 on: out_ids, events and cs_read_agents carry the full id, the snapshot its low 32 bits, also
+    after renumberings."""
+    first = 2 ** 40
+    monkeypatch.setenv("CS_FIRST_AGENT_ID", str(first))
+    monkeypatch.setenv("CS_DEVICE_ID_LIMIT", "4096")
+    pts, grid, extent, group = scenes.uniform_crowd(1000, seed=9, cell_size=2.0, room=20.0)
+    sim = Simulation(LocationHash2D(**grid), flags=flags | CS_CFG_WIDE_IDS)
+    rec = Recorder(0)
+    sim.add_event_listener(rec)
+    ids = scenes.add_counterflow(sim, pts, group, scenes.CREEP_SPEED, Zanlungo(*scenes.METRIC_ZANLUNGO), 2.0)
+    assert sorted(int(i) for i in ids) == list(range(first, first + 1000))
+    keep = list(range(first, first + 1000))
+    spot = np.array([[extent + 15.0, extent + 15.0]])
+    for r in range(12):  # 12 x 500 ids through a 4096-id device space
+        more = sim.add_agents(np.repeat(spot, 500, axis=0) + np.arange(500)[:, None] * 0.01, StubHighLevelPlan((0.0, 0.0)),
+                              NoLocalPlan(), 1.0)
+        assert more == list(range(first + 1000 + 500 * r, first + 1500 + 500 * r))
+        sim.step(0.05)
+        for i in more[:-2]:
+            sim.remove_agents(i)
+        keep += more[-2:]
+    sim.step(0.05)
+    a = sim.read_agents()
+    assert [int(i) for i in a["id"]] == keep
+    added = [i for k, i in rec.events if k == "spawned"]
+    removed = [i for k, i in rec.events if k == "destroyed"]
+    assert added == list(range(first, first + 7000))
+    assert sorted(removed) == sorted(set(added) - set(keep))
+    sim.request_snapshot()
+    snap, _ = sim.snapshot(wait=True)
+    assert len(snap) == len(a)
+    low = (a["id"] & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    assert (np.sort(snap["id"]) == np.sort(low)).all() and len(np.unique(low)) == len(a)
+
+
+@FLAGS
+def test_a_crowd_too_large_for_the_device_ids_is_refused(flags, monkeypatch):
+    """More than limit / 2 live agents: a renumbering cannot make room, the add is refused with the live count in the
+    message, and the engine carries on."""
+    monkeypatch.setenv("CS_DEVICE_ID_LIMIT", "4096")
+    monkeypatch.delenv("CS_FIRST_AGENT_ID", raising=False)
+    pts, grid, extent, group = scenes.uniform_crowd(2100, seed=4, cell_size=2.0)
+    sim = Simulation(LocationHash2D(**grid), flags=flags | CS_CFG_WIDE_IDS)
+    ids = scenes.add_counterflow(sim, pts, group, scenes.CREEP_SPEED, Zanlungo(*scenes.METRIC_ZANLUNGO), 2.0)
+    sim.step(0.05)
+    more = scenes.jittered_lattice(2000, 0.3, (1.0, 0.5), 0.1, 3, columns=150)  # below the crowd
+    with pytest.raises(CrowdSimError, match="agent id space exhausted: 2100 live agents"):
+        sim.add_agents(more, StubHighLevelPlan((0.0, 0.0)), NoLocalPlan(), 1.0)
+    assert len(sim) == 2100
+    sim.step(0.05)
+    for i in sorted(int(v) for v in ids)[:1200]:
+        sim.remove_agents(i)
+    # 900 live agents: a renumbering makes room (the refused add consumed no ids)
+    got = sim.add_agents(more, StubHighLevelPlan((0.0, 0.0)), NoLocalPlan(), 1.0)
+    assert got == list(range(2100, 4100))
+    sim.step(0.05)
+    a = sim.read_agents()
+    assert [int(i) for i in a["id"]] == sorted(int(v) for v in ids)[1200:] + got
