@@ -98,15 +98,19 @@ class Recorder(EventListener):
 STEPS, CHURN = 140, 250
 
 
-def _renumbering_scene(sim, shift, steps=STEPS):
+def _renumbering_scene(sim, shift, steps=STEPS, churn=CHURN, extra=0):
     """~600 agents in contact with an id-parity planner, 16 agents of a host local planner, looping and one-way
-    source-sinks (TargetPlan: set_target / remove callbacks) and CHURN parked agents added and removed again (by id)
-    every step: ~36,000 ids in all.  Returns what has to equal the oracle's, with ids shifted by `shift`."""
+    source-sinks (TargetPlan: set_target / remove callbacks) and `churn` parked agents added and removed again (by id)
+    every step: ~36,000 ids in all.  `extra` more agents in contact stand in a block at x >= 104 (the grid must be
+    wider then).  Returns what has to equal the oracle's, with ids shifted by `shift`."""
     rec = Recorder(shift)
     sim.add_event_listener(rec)
     zan = Zanlungo(*scenes.METRIC_ZANLUNGO)
     crowd = scenes.jittered_lattice(600, 0.6, (50.0, 30.0), 0.2, 11, columns=30)
     sim.add_agents(crowd, IdParityHighLevelPlan((0.0, 0.02)), zan, 2.0)
+    if extra:
+        block = scenes.jittered_lattice(extra, 0.6, (104.0, 4.0), 0.2, 13, columns=90)
+        sim.add_agents(block, IdParityHighLevelPlan((0.0, 0.02)), zan, 2.0)
     lp = LoggingPlanner(shift)
     sim.add_agents(scenes.jittered_lattice(16, 0.8, (30.0, 50.0), 0.2, 12, columns=4), IdParityHighLevelPlan((0.05, 0.0)),
                    lp, 2.0)
@@ -123,7 +127,7 @@ def _renumbering_scene(sim, shift, steps=STEPS):
     parked = StubHighLevelPlan((0.0, 0.0))
     last, per_step, queries = [], [], []
     for s in range(steps):
-        spots = np.stack([rng.uniform(2.0, 20.0, CHURN), rng.uniform(70.0, 96.0, CHURN)], axis=1)
+        spots = np.stack([rng.uniform(2.0, 20.0, churn), rng.uniform(70.0, 96.0, churn)], axis=1)
         now = sim.add_agents(spots, parked, NoLocalPlan(), 1.0)
         for i in last:
             sim.remove_agents(i)
