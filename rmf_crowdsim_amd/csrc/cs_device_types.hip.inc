@@ -74,6 +74,9 @@ struct GroupDev {
   float hvx, hvy;
   int32_t sink;  // owning source-sink slot or -1
   uint32_t hlp;  // planner handle (the route book is kept per planner)
+  // |fut|^2 in fixed units from which every forward force term is exactly +0 (zanlungo_forward_vanishes), set by the
+  // host (cs_engine::upload_groups); NaN: never
+  float vanish2;
 };
 
 struct SinkDev {
@@ -135,7 +138,7 @@ struct Counters {
   // the border windows had packed, so the engine is poisoned.
   uint32_t border_done, border_flag, n_early_stalled;
 #ifdef CS_TILE_TRIPS  // diagnostic build (tools/trip_counts.sh): per-wave loop trips of the tiled kernel, cs_kernel_stat(100 + i)
-  uint32_t dbg[12];
+  uint32_t dbg[17];
 #endif
 };
 
@@ -386,6 +389,46 @@ __device__ __forceinline__ void zanlungo_forward_force(float rpx, float rpy, flo
   const float scale = c.mag * fast_exp2((c.two_R - dist) * c.k_exp) * inv_n;
   fx = __builtin_fmaf(px, scale, fx);
   fy = __builtin_fmaf(py, scale, fy);
+}
+
+// v_exp_f32 (fast_exp2) returns +0 for every input at or below -ZAN_EXP2_ZERO.  It flushes results below 2^-126 to +0 in
+// the kernels' denormal mode (the engine is built without -ffast-math: f32 denormals on); an exhaustive sweep on gfx950
+// found +0 for every input below -126 and the smallest non-zero result at -126 (tools/exp2_underflow.hip).  160 keeps
+// the test right even for an exp2 that returned denormals: 2^-160 lies far below half the smallest one, 2^-150.
+#define ZAN_EXP2_ZERO 160.0f
+
+// The force pass's pre-test (k_step_tiled): true when every forward term of this agent whose direction is not NaN has
+// fast_exp2(...) == +0 in zanlungo_forward_force, for any neighbour the lean filter can list (|rp| < |rs|, rs = S
+// eyesight).  The kernel's per-entry check (forward_terms_vanish) takes the agent off the fast path if any forward entry
+// has the NaN direction (s = +-0 or NaN), so the argument below may assume rp != 0 for every forward entry: rp is then a
+// non-zero integer vector, |rp| >= 1.  Ts is the agent's t_i in fixed units, c its context, vanish2 the group's bound.
+//   * The argument: dist >= Z / k_exp + max(two_R, 0) (Z = ZAN_EXP2_ZERO) with a relative margin of a few ulps gives
+//     (two_R - dist) * k_exp <= -Z after both roundings (the subtraction and the product, 2^-24 each), for k_exp > 0
+//     finite and normal and two_R finite.  An infinite dist (d2 overflowed) gives -inf, and exp2(-inf) = +0 too.
+//   * dist >= |fut - rp| (1 - 2^-21): dx, dy (2^-24 each), dy * dy and the fma (2^-24 each), v_sqrt_f32 (1 ulp, 2^-23).
+//     Nothing underflows: |fut - rp| >= 2^-12 |fut| >= 2^-12 (below, and |fut| > |rp| >= 1).
+//   * |fut - rp| >= |fut| - |rp|, and a listed neighbour has |rp| < |rs| (1 + 2^-24) (sight_margin < 0 with nr2 rounded
+//     once; the fmas only round the sign-correct result).
+// So |fut| >= (|rs| + max(two_R, 0) + Z / k_exp) (1 + 2^-20) suffices.  The host computes b = that sum with rs, two_R
+// and k_exp formed exactly as make_force_ctx forms them, in double, times (1 + 2^-10), and stores b^2 rounded up
+// (GroupDev::vanish2; NaN unless k_exp is normal and finite, rs and two_R finite, and b^2 fits).  The kernel's one
+// rounding, |fut|^2 (the product and the fma, under 2^-23), leaves whatever passes a margin of at least 2^-11.  fut is
+// the very (futx, futy) the force reads, so its own rounding does not enter.  mag must be finite (mag * 0 = +-0), and
+// 0 < t_i < inf.  A NaN anywhere fails a comparison: the agent is no candidate.
+__device__ __forceinline__ bool zanlungo_forward_vanishes(const ForceCtx& c, float Ts, float vanish2) {
+  const float fut2 = __builtin_fmaf(c.futx, c.futx, c.futy * c.futy);
+  return Ts > 0.0f && Ts < f_inf() && fabsf(c.mag) < f_inf() && fut2 >= vanish2;
+}
+// GroupDev::vanish2 for a Zanlungo group (host side of zanlungo_forward_vanishes)
+inline float zanlungo_vanish2(float eyesight, float R, float D, const GridDev& g) {
+  const float k_exp = 1.44269504088896341f / D * g.fix_inv;  // as make_force_ctx
+  const float rs = eyesight * g.fix_scale, two_R = R * 2.0f * g.fix_scale;
+  if (!(k_exp >= 0x1p-126f && k_exp < HUGE_VALF && std::fabs(rs) < HUGE_VALF && std::fabs(two_R) < HUGE_VALF))
+    return std::nanf("");
+  const double b = ((double)std::fabs(rs) + std::max((double)two_R, 0.0) + (double)ZAN_EXP2_ZERO / (double)k_exp) *
+                   (1.0 + 0x1p-10);
+  const float b2 = std::nextafter((float)(b * b), HUGE_VALF);  // (rounded up)
+  return b2 < HUGE_VALF ? b2 : std::nanf("");
 }
 
 // RMFPlanner::route_plans_by_location (rmf/mod.rs:90) on the device: an open-addressing table of

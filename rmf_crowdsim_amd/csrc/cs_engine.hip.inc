@@ -727,6 +727,7 @@ struct cs_engine {
       d.D = (float)z.force_distance;
       d.inv_mass = 1.0f / (float)z.agent_mass;  // force * (1/m), zanlungo.rs:216
       d.R = (float)z.agent_radius;
+      d.vanish2 = zanlungo_vanish2(d.eyesight, d.R, d.D, gdev);
       const cs_hlp_desc& h = hlps[groups[i].hlp];
       d.hlp_kind = h.kind;
       d.hvx = (float)h.vx;

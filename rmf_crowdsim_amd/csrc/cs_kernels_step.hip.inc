@@ -1389,6 +1389,38 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
         if (wave_any(((mask & ~in_lds) | mask2) != 0ull)) run_force_impl(mask & ~in_lds, mask2, std::true_type{});
       }
     };
+    // The check of a lane that passed the force pre-test (zanlungo_forward_vanishes): true when none of the entries of
+    // `mask` (LDS rows only) has the NaN direction.  Each term's exp2 is then +0, so the term leaves fx, fy at +0.  The
+    // s is bit for bit the one of zanlungo_forward_force: there s = |fma(px, dy, -(py dx))| with (px, py) = +-(rpy, -rpx).
+    // Unflipped that is |fma(rpy, dy, c)| with c = rpx dx rounded (-((-rpx) dx) = c: negations are exact); flipped it is
+    // |fma(-rpy, dy, -c)| = |-fma(rpy, dy, c)| (negating a factor and the addend negates the exact result, and rounding
+    // to nearest is symmetric).  No sqrt, rsq or exp here: that is the saving.  A forward entry at the agent's own
+    // position (rp = 0) has s = 0 (or NaN) and fails.
+    // `s > 0` fails for +-0 and NaN: exactly when (bits(s) << 1) - 1 exceeds 0xFEFFFFFF (+-inf passes, as there), kept
+    // as a running maximum in a register.  s is never a denormal: rpx, rpy are integers; for rpx != 0, dx = futx - rpx is 0
+    // or at least 2^-24 in magnitude (near an integer of magnitude >= 1 a float is a multiple of 2^-24), so rpx dx and its
+    // rounding are 0 or multiples of 2^-47; for rpx == 0 that term is 0 (or NaN for an infinite dx).  The same holds for
+    // rpy dy, so a non-zero finite s is at least 2^-47, and the bit test agrees with the comparison in any denormal mode.
+    // The mask is walked one 32-bit word at a time (a 64-bit lowest-bit search and clear cost 7 VALU per entry, a 32-bit
+    // one 3); entries 32..63 are the few beyond the first word.  (Two entries per trip, and a lane mask for the result,
+    // measured slower: more scalar instructions per entry.)
+    auto forward_terms_vanish = [&](unsigned long long mask) {
+      uint32_t worst = 0u;
+      auto word = [&](uint32_t w, uint32_t row0) {
+        const entry_t* __restrict__ lp = my_list + row0 * TILE_THREADS;
+        while (w) {
+          const uint32_t k = (uint32_t)__builtin_ctz(w);
+          w &= w - 1u;
+          float rpx, rpy;
+          rel((uint32_t)lp[k * TILE_THREADS], rpx, rpy);
+          const float s = __builtin_fmaf(rpy, fc.futy - rpy, rpx * (fc.futx - rpx));
+          worst = max(worst, (__float_as_uint(s) << 1) - 1u);
+        }
+      };
+      word((uint32_t)mask, 0u);
+      word((uint32_t)(mask >> 32), 32u);
+      return worst <= 0xFEFFFFFFu;
+    };
     // masks of the first c list entries
     auto run_force_first = [&](uint32_t c) {
       const unsigned long long lo = c >= 64u ? ~0ull : ((1ull << c) - 1ull);
@@ -1630,10 +1662,54 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
 #endif
     if (mine && T != f_inf()) fc = make_force_ctx(o.v.x, o.v.y, T, grp, g);
     else fc = ForceCtx{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // Forces that provably vanish: an agent whose collision horizon lies far away (|v| t_i beyond its sight by more than
+    // the exp2 underflow distance, zanlungo_forward_vanishes) has exactly +0 in every forward term.  Such a lane checks
+    // its entries for the NaN direction only (forward_terms_vanish) and then passes mask 0 to the full loop: a wave of
+    // such lanes skips it, one with a lane whose check failed runs it for that lane.  Its fx, fy stay +0, the bits the full
+    // loop produces: there scale = (mag * (+0)) * inv_n = +-0 (mag finite, inv_n = rsq(d2) finite and > 0 for d2 >= 1),
+    // and fma(px, +-0, +0) = +0 for a finite px (px * +-0 is exact; +-0 + +0 = +0), term after term from fx = fy = +0.
+    // Lanes that fail the pre-test or the check run the unchanged loop, so every NaN comes from there, with its bits.
+    // (The spilled-row form, the drained lists of `flushed` and every ablation (TILE_DEBUG) keep the full loop for every
+    // lane, so that ablation timings still compare with the recorded ones.)
+    const bool vanish = mine && T != f_inf() && zanlungo_forward_vanishes(fc, T, grp.vanish2);
+#ifdef CS_TILE_TRIPS
+    {  // the pre-test: lanes that pass, waves in which every lane with a finite t_i passes, their forward entries
+      const unsigned long long finite = __ballot(mine && T != f_inf()), pass = __ballot(vanish);
+      const uint32_t all = (mine && T != f_inf()) ? (uint32_t)__popcll(fwd) + (uint32_t)__popcll(fwd2) : 0u;
+      uint32_t ent = vanish ? all : 0u, ent_all = all;
+      for (int d = 32; d; d >>= 1) {
+        ent += __shfl_xor(ent, d);
+        ent_all += __shfl_xor(ent_all, d);
+      }
+      if ((tid & 63u) == 0u) {
+        atomicAdd(&E.ctr->dbg[11], (uint32_t)__popcll(pass));
+        if (finite != 0ull && (finite & ~pass) == 0ull) atomicAdd(&E.ctr->dbg[12], 1u);
+        atomicAdd(&E.ctr->dbg[13], ent);
+        atomicAdd(&E.ctr->dbg[16], ent_all);
+      }
+    }
+#endif
     // lanes with t_i = inf take no force (zanlungo.rs:211)
     if (TILE_DEBUG(64u)) {
     } else if (!__any(flushed)) {
-      run_force((T != f_inf()) ? fwd : 0ull, (T != f_inf()) ? fwd2 : 0ull);
+      unsigned long long m = (T != f_inf()) ? fwd : 0ull;
+      // Only a wave in which every lane with forward entries is a candidate takes the check.  Elsewhere the loop's trip
+      // count stays some other lane's, and the check would only add to it (the creep scene, where 0.75 % of the lanes
+      // pass, ran its step kernel 5 % slower with the check in every wave that had a candidate).
+      const unsigned long long work = __builtin_amdgcn_ballot_w64(m != 0ull);
+      if (!TILE_DEBUG(~0u) && !spilling && work != 0ull && (work & ~__builtin_amdgcn_ballot_w64(vanish)) == 0ull) {
+        if (m != 0ull && forward_terms_vanish(m)) m = 0ull;
+#ifdef CS_TILE_TRIPS
+        {  // lanes that took the fast path, waves whose full loop it emptied
+          const unsigned long long fast = __ballot(vanish && m == 0ull);
+          if ((tid & 63u) == 0u) {
+            atomicAdd(&E.ctr->dbg[14], (uint32_t)__popcll(fast));
+            if (!wave_any(m != 0ull)) atomicAdd(&E.ctr->dbg[15], 1u);
+          }
+        }
+#endif
+      }
+      run_force(m, (T != f_inf()) ? fwd2 : 0ull);
     } else {
       cnt = 0;
       if (T == f_inf()) {
