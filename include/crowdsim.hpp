@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "crowdstep.h"
+#include "crowdstep_state.h"
 
 namespace rmf_crowdsim {
 
@@ -39,6 +40,21 @@ struct Agent {  // lib.rs:46-65
   std::size_t next_waypoint = 0;
   double eyesight_range = 0;
 };
+
+// one record of write_agents (include/crowdstep_state.h): the fields of `a` that a write can set (eyesight_range is
+// carried along and ignored; orientation and angular_vel are not writable)
+inline cs_agent_view agent_view_of(const Agent& a) {
+  cs_agent_view v{};
+  v.id = a.agent_id;
+  v.x = a.position.x;
+  v.y = a.position.y;
+  v.vx = a.velocity.x;
+  v.vy = a.velocity.y;
+  v.next_waypoint = a.next_waypoint;
+  v.eyesight_range = a.eyesight_range;
+  return v;
+}
+constexpr uint32_t kWriteAll = CS_WRITE_POSITION | CS_WRITE_VELOCITY | CS_WRITE_NEXT_WAYPOINT;
 
 struct EventListener {  // lib.rs:22-33
   virtual ~EventListener() = default;
@@ -315,6 +331,19 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     after_mutation();
     if (rc != 0) throw std::runtime_error(cs_last_error(engine_));
   }
+  // agents.get_mut(&id) (lib.rs:71) for a batch, by id: the written fields (CS_WRITE_* bits) become the agents'
+  // start-of-step state.  All or nothing: a refused batch throws and changes nothing.  Edit a copy of `agents` and
+  // write it back: std::vector<Agent> edited = ...; sim.write_agents(edited, CS_WRITE_POSITION);
+  void write_agents(const std::vector<cs_agent_view>& records, uint32_t fields = kWriteAll) {
+    const int rc = cs_write_agents(engine_, records.data(), records.size(), fields);
+    after_mutation();
+    if (rc != 0) throw std::runtime_error(cs_last_error(engine_));
+  }
+  void write_agents(const std::vector<Agent>& edited, uint32_t fields = kWriteAll) {
+    std::vector<cs_agent_view> v;
+    for (const Agent& a : edited) v.push_back(agent_view_of(a));
+    write_agents(v, fields);
+  }
   void step(std::chrono::duration<double> dur) {  // lib.rs:195-383
     cs_step_report rep;
     int rc = cs_step(engine_, dur.count(), &rep);
@@ -471,6 +500,18 @@ class TiledSimulation {
     const int rc = cs_mesh_remove_agent(mesh_, agent);
     refresh();
     if (rc != 0) throw std::runtime_error(cs_mesh_last_error(mesh_));
+  }
+  // Simulation::write_agents on the mesh: an agent written into a cell another tile owns moves there (collective in the
+  // distributed forms: every rank passes the same batch)
+  void write_agents(const std::vector<cs_agent_view>& records, uint32_t fields = kWriteAll) {
+    const int rc = cs_mesh_write_agents(mesh_, records.data(), records.size(), fields);
+    refresh();
+    if (rc != 0) throw std::runtime_error(cs_mesh_last_error(mesh_));
+  }
+  void write_agents(const std::vector<Agent>& edited, uint32_t fields = kWriteAll) {
+    std::vector<cs_agent_view> v;
+    for (const Agent& a : edited) v.push_back(agent_view_of(a));
+    write_agents(v, fields);
   }
   void step(std::chrono::duration<double> dur) {  // lib.rs:195-383
     cs_step_report rep;

@@ -3,7 +3,8 @@
 Host-side mirror of the reference trait surface over the C ABI of the HIP engine
 (include/crowdstep.h, csrc/crowdstep_hip.hip).  There is no CPU fallback.
 """
-from ._abi import (CS_CFG_DEFAULT, CS_CFG_DENSE, CS_CFG_FORCE_GATHER, CS_CFG_FORCE_TILED, CS_CFG_WIDE_IDS)
+from ._abi import (CS_CFG_DEFAULT, CS_CFG_DENSE, CS_CFG_FORCE_GATHER, CS_CFG_FORCE_TILED, CS_CFG_WIDE_IDS,
+                   CS_WRITE_NEXT_WAYPOINT, CS_WRITE_POSITION, CS_WRITE_VELOCITY)
 from .simulation import (Agent, CrowdGenerator, CrowdSimError, EventListener, HighLevelPlanner,
                          IdParityHighLevelPlan, LocalPlanner, LocationHash2D, MonotonicCrowd,
                          NoHighLevelPlan, NoLocalPlan, PoissonCrowd, RouteFollower, SeededPoissonCrowd, Simulation,
@@ -16,5 +17,5 @@ __all__ = [
     "NoHighLevelPlan", "NoLocalPlan", "PoissonCrowd", "RouteFollower", "SeededPoissonCrowd", "Simulation",
     "SourceSink", "SpatialIndex",
     "StubHighLevelPlan", "Zanlungo", "CS_CFG_DEFAULT", "CS_CFG_DENSE", "CS_CFG_FORCE_GATHER",
-    "CS_CFG_FORCE_TILED", "CS_CFG_WIDE_IDS",
+    "CS_CFG_FORCE_TILED", "CS_CFG_WIDE_IDS", "CS_WRITE_NEXT_WAYPOINT", "CS_WRITE_POSITION", "CS_WRITE_VELOCITY",
 ]

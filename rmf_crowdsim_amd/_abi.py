@@ -245,6 +245,17 @@ SYMBOLS = {
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
 
+# include/crowdstep_state.h: entry points of the HIP engine that the test oracle does not implement (kept apart from
+# SYMBOLS, which is crowdstep.h symbol for symbol and what both libraries export)
+CS_WRITE_POSITION = 1
+CS_WRITE_VELOCITY = 2
+CS_WRITE_NEXT_WAYPOINT = 4
+CS_WRITE_ALL = CS_WRITE_POSITION | CS_WRITE_VELOCITY | CS_WRITE_NEXT_WAYPOINT
+STATE_SYMBOLS = {
+    "cs_write_agents": (C.c_int, [C.c_void_p, C.POINTER(AgentView), C.c_size_t, C.c_uint32]),
+    "cs_mesh_write_agents": (C.c_int, [C.c_void_p, C.POINTER(AgentView), C.c_size_t, C.c_uint32]),
+}
+
 
 def bind(lib):
     """Attach restype/argtypes for every ABI symbol; raises AttributeError if one is missing."""
@@ -255,4 +266,16 @@ def bind(lib):
     version = lib.cs_abi_version()
     if version != CS_ABI_VERSION:
         raise RuntimeError(f"crowdstep ABI mismatch: library {version}, bindings {CS_ABI_VERSION}")
+    return lib
+
+
+def bind_state(lib):
+    """Attach restype/argtypes for the symbols of include/crowdstep_state.h (the HIP engine only).  A build without them
+    (an older library chosen with CS_LIB_PATH for a timing comparison) loads; its write_agents then raises."""
+    for name, (restype, argtypes) in STATE_SYMBOLS.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            continue
+        fn.restype = restype
+        fn.argtypes = argtypes
     return lib

@@ -46,6 +46,7 @@ def _stale():
     built = os.path.getmtime(LIB_PATH)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
     deps.append(os.path.join(REPO_ROOT, "include", "crowdstep.h"))
+    deps.append(os.path.join(REPO_ROOT, "include", "crowdstep_state.h"))
     return any(os.path.getmtime(d) > built for d in deps if os.path.isfile(d))
 
 
@@ -86,5 +87,5 @@ def load():
         import torch  # noqa: F401
     except ImportError:
         pass
-    _lib = _abi.bind(ctypes.CDLL(lib_path))
+    _lib = _abi.bind_state(_abi.bind(ctypes.CDLL(lib_path)))
     return _lib

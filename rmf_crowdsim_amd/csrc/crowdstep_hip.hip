@@ -15,6 +15,8 @@
 //   cs_kernels_aux.hip.inc    k_halo_pack/unpack (tiles), k_spawn (lib.rs:199-254), radius query
 //   cs_engine.hip.inc         the host engine: step state machine, tables, tiles, events
 //   cs_rccl.hip.inc           RCCL bound at first use (halo transport of a tile)
+//   cs_mesh.hip.inc           a crowd cut into tiles behind one handle (cs_mesh_*)
+//   cs_agent_write.hip.inc    writing agents between steps, by id (include/crowdstep_state.h)
 //   this file                 includes + the extern "C" boundary
 //
 // Device state is f32 and CELL-RELATIVE: an agent is (stored cell, offset from
@@ -38,6 +40,7 @@
 #include <vector>
 
 #include "crowdstep.h"
+#include "crowdstep_state.h"
 
 #define CS_INVALID_CELL 0xFFFFFFFFu
 #define CS_MAX_GROUPS 1048575u  // the group index travels in 16 or 20 bits of `meta` (GridDev::grp_bits)
@@ -97,7 +100,7 @@ void cs_destroy(cs_engine* e) {
   hipFree(e->route_desc_dev); hipFree(e->route_xy_dev); hipFree(e->route_book_dev); hipFree(e->hlp_scale_dev); hipFree(e->route_pending_dev);
   hipFree(e->groups_dev); hipFree(e->sinks_dev); hipFree(e->waypoints_dev);
   hipFree(e->src_cell_start); hipFree(e->src_sorted); hipFree(e->src_occupied);
-  hipFree(e->want_dev); hipFree(e->spawned_slots_dev); hipFree(e->spawn_scratch); hipHostFree(e->want_host); hipFree(e->blk_desc); hipFree(e->blk_desc_back); hipFree(e->n_blocks_dev); hipFree(e->n_blocks_back); hipFree(e->band_prefix); hipFree(e->tile_spill); hipFree(e->spawn_rec_dev); hipFree(e->find_dev); hipFree(e->step_flags_dev); hipFree(e->query_scratch); hipFree(e->scan_tile_sums);
+  hipFree(e->want_dev); hipFree(e->spawned_slots_dev); hipFree(e->spawn_scratch); hipHostFree(e->want_host); hipFree(e->blk_desc); hipFree(e->blk_desc_back); hipFree(e->n_blocks_dev); hipFree(e->n_blocks_back); hipFree(e->band_prefix); hipFree(e->tile_spill); hipFree(e->spawn_rec_dev); hipFree(e->find_dev); hipFree(e->step_flags_dev); hipFree(e->query_scratch); hipFree(e->scan_tile_sums); hipFree(e->write_scratch);
   for (auto& t : e->timed) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
   for (auto ev : e->event_pool) hipEventDestroy(ev);
   if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
@@ -1239,3 +1242,4 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 }  // extern "C"
 
 #include "cs_mesh.hip.inc"
+#include "cs_agent_write.hip.inc"

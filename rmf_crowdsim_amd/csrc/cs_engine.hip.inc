@@ -2707,4 +2707,7 @@ struct cs_engine {
     if (sorted) return 0;
     return rebuild();
   }
+
+  void* write_scratch = nullptr;  // device scratch of cs_write_agents (grown as needed, never shrunk: cs_agent_write.hip.inc)
+  size_t write_scratch_bytes = 0;
 };

@@ -396,6 +396,80 @@ def source_sink_desc(source_sink, handle_of):
 AGENT_DTYPE = np.dtype([("id", "<u8"), ("x", "<f8"), ("y", "<f8"), ("vx", "<f8"), ("vy", "<f8"),
                         ("next_waypoint", "<u8"), ("eyesight_range", "<f8")])
 
+# the fields write_agents sets (include/crowdstep_state.h); eyesight_range, orientation and angular_vel are not writable
+WRITE_FIELDS = {"position": _abi.CS_WRITE_POSITION, "velocity": _abi.CS_WRITE_VELOCITY,
+                "next_waypoint": _abi.CS_WRITE_NEXT_WAYPOINT}
+
+
+def write_mask(fields):
+    """CS_WRITE_* bits of `fields`: an int mask, one name of WRITE_FIELDS or several."""
+    if isinstance(fields, (int, np.integer)):
+        return int(fields)
+    if isinstance(fields, str):
+        fields = (fields,)
+    mask = 0
+    for name in fields:
+        if name not in WRITE_FIELDS:
+            raise CrowdSimError(f"write_agents: {name!r} is not writable (writable: {', '.join(WRITE_FIELDS)})")
+        mask |= WRITE_FIELDS[name]
+    return mask
+
+
+def write_records(records):
+    """`records` as a contiguous AGENT_DTYPE array (the structured array read_agents returns, or any with its names)."""
+    arr = np.asarray(records)
+    if arr.dtype != AGENT_DTYPE:
+        if arr.dtype.names is None or "id" not in arr.dtype.names:
+            raise CrowdSimError("write_agents takes the structured array read_agents returns (AGENT_DTYPE)")
+        out = np.zeros(arr.shape, dtype=AGENT_DTYPE)
+        for name in AGENT_DTYPE.names:
+            if name in arr.dtype.names:
+                out[name] = arr[name]
+        arr = out
+    return np.ascontiguousarray(arr.reshape(-1))
+
+
+def _agents_dict(arr):
+    return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
+                                int(r["next_waypoint"]), float(r["eyesight_range"]))
+            for r in arr}
+
+
+def edited_agents(agents, read):
+    """(records, mask): the entries of an `agents` dict whose position, velocity or next_waypoint differ (bit for bit)
+    from `read`, the array the dict was made from, and the union of the fields that changed.  Raises CrowdSimError if a
+    field that cannot be written changed, or if the dict holds an id that was not read."""
+    by_id = {int(r["id"]): k for k, r in enumerate(read)}
+    extra = [i for i in agents if i not in by_id]
+    if extra:
+        raise CrowdSimError(f"commit_agents: agent {min(extra)} was not read; commit_agents writes existing agents "
+                            "(add_agents adds them)")
+    rows, mask = [], 0
+    for aid, a in agents.items():
+        r = read[by_id[aid]]
+        if (int(a.agent_id) != aid or float(a.eyesight_range) != float(r["eyesight_range"]) or a.orientation != 0.0
+                or a.angular_vel != 0.0):
+            raise CrowdSimError(f"commit_agents: agent {aid}: only position, velocity and next_waypoint are writable "
+                                "(agent_id, eyesight_range, orientation and angular_vel changed)")
+        pos = np.asarray(a.position, dtype=np.float64).reshape(2)
+        vel = np.asarray(a.velocity, dtype=np.float64).reshape(2)
+        wp = int(a.next_waypoint)
+        if wp < 0:
+            raise CrowdSimError(f"commit_agents: agent {aid}: next_waypoint {wp} is negative")
+        m = 0
+        if pos.tobytes() != np.array([r["x"], r["y"]]).tobytes():
+            m |= _abi.CS_WRITE_POSITION
+        if vel.tobytes() != np.array([r["vx"], r["vy"]]).tobytes():
+            m |= _abi.CS_WRITE_VELOCITY
+        if wp != int(r["next_waypoint"]):
+            m |= _abi.CS_WRITE_NEXT_WAYPOINT
+        if m:
+            row = r.copy()
+            row["x"], row["y"], row["vx"], row["vy"], row["next_waypoint"] = pos[0], pos[1], vel[0], vel[1], wp
+            rows.append(row)
+            mask |= m
+    return np.array(rows, dtype=AGENT_DTYPE), mask
+
 
 class Simulation:
     """Simulation<LocationHash2D>, lib.rs:69-383, on one MI355X."""
@@ -596,12 +670,36 @@ class Simulation:
         """`pub agents: HashMap<AgentId, Agent>` (lib.rs:71), read back lazily."""
         if self._agents_cache is None:
             arr = self.read_agents()
-            self._agents_cache = {
-                int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]),
-                                    np.array([r["vx"], r["vy"]]), int(r["next_waypoint"]),
-                                    float(r["eyesight_range"]))
-                for r in arr}
+            self._agents_cache = _agents_dict(arr)
+            self._agents_read = arr  # (what commit_agents compares the dict with)
         return self._agents_cache
+
+    def write_agents(self, records, fields=_abi.CS_WRITE_ALL):
+        """`agents.get_mut(&id)` (lib.rs:71) for a batch: `records` is the structured array read_agents returns
+        (AGENT_DTYPE), `fields` an int mask of _abi.CS_WRITE_* bits or names from WRITE_FIELDS ("position",
+        "velocity", "next_waypoint").  The written values become the agents' start-of-step state; eyesight_range is
+        ignored.  All or nothing: a refused batch raises CrowdSimError and changes nothing (include/crowdstep_state.h)."""
+        fn = getattr(self._lib, "cs_write_agents", None)
+        if fn is None:
+            raise CrowdSimError(f"write_agents needs the HIP engine: the {self.backend} library does not implement "
+                                "include/crowdstep_state.h")
+        arr = write_records(records)
+        rc = fn(self._engine, arr.ctypes.data_as(C.POINTER(_abi.AgentView)), len(arr), write_mask(fields))
+        self._agents_cache = None
+        if rc != 0:
+            raise self._err()
+        return len(arr)
+
+    def commit_agents(self):
+        """Write back the entries of `agents` whose position, velocity or next_waypoint were edited since they were
+        read (the reference's `agents.get_mut(&id).position = p`, made explicit).  Raises CrowdSimError if a field that
+        cannot be written changed.  Returns the number of agents written."""
+        if self._agents_cache is None:
+            return 0
+        rows, mask = edited_agents(self._agents_cache, self._agents_read)
+        if not len(rows):
+            return 0
+        return self.write_agents(rows, mask)
 
     def __len__(self):
         return int(self._lib.cs_agent_count(self._engine))

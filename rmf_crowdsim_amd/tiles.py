@@ -496,6 +496,7 @@ class NativeTileMesh:
         self._host_lp_of_agent, self._host_lp_of_sink = {}, {}  # LocalPlanner::remove_agent follows the destroy events
         self.last_report = None
         self.shape = (desc.tiles_x, desc.tiles_y)
+        self._agents_cache = self._agents_read = None  # (the `agents` dict and the array it was made from)
 
     def __del__(self):
         if getattr(self, "_mesh", None):
@@ -548,6 +549,7 @@ class NativeTileMesh:
         rc = self._lib.cs_mesh_add_agents(self._mesh, pts.ctypes.data_as(C.POINTER(C.c_double)), len(pts),
                                           self._handle(high_level_planner), self._handle(local_planner), float(eyesight),
                                           ids.ctypes.data_as(C.POINTER(C.c_uint64)))
+        self._agents_cache = None
         if getattr(local_planner, "_host_code", False) and rc == 0:
             self._lib.cs_mesh_event_recording(self._mesh, 1)
             for i in ids:
@@ -578,6 +580,7 @@ class NativeTileMesh:
 
     def remove_agents(self, agent):
         rc = self._lib.cs_mesh_remove_agent(self._mesh, int(agent))
+        self._agents_cache = None
         self._dispatch()
         if rc != 0:
             raise self._err()
@@ -586,6 +589,7 @@ class NativeTileMesh:
         rep = _abi.StepReport()
         need = report or bool(self._listeners) or bool(self._host_lp_of_agent) or bool(self._host_lp_of_sink)
         rc = self._lib.cs_mesh_step(self._mesh, float(dur), self._C.byref(rep) if need else None)
+        self._agents_cache = None
         if need:
             self.last_report = rep.as_dict()
         self._dispatch()
@@ -639,6 +643,37 @@ class NativeTileMesh:
 
     def __len__(self):
         return int(self._lib.cs_mesh_agent_count(self._mesh))
+
+    @property
+    def agents(self):
+        """`pub agents` (lib.rs:71) of the whole crowd, read back lazily (a fresh dict after every call that changes it)."""
+        from .simulation import _agents_dict
+        if self._agents_cache is None:
+            arr = self.read_agents()
+            self._agents_cache, self._agents_read = _agents_dict(arr), arr
+        return self._agents_cache
+
+    def write_agents(self, records, fields=_abi.CS_WRITE_ALL):
+        """Simulation.write_agents on the mesh (cs_mesh_write_agents): an agent written into a cell another tile owns
+        moves there.  Collective in the distributed form: every rank passes the same batch."""
+        from .simulation import write_mask, write_records
+        arr = write_records(records)
+        rc = self._lib.cs_mesh_write_agents(self._mesh, arr.ctypes.data_as(self._C.POINTER(_abi.AgentView)), len(arr),
+                                            write_mask(fields))
+        self._agents_cache = None
+        if rc != 0:
+            raise self._err()
+        return len(arr)
+
+    def commit_agents(self):
+        """Simulation.commit_agents on the mesh (collective in the distributed form)."""
+        from .simulation import edited_agents
+        if self._agents_cache is None:
+            return 0
+        rows, mask = edited_agents(self._agents_cache, self._agents_read)
+        if not len(rows):
+            return 0
+        return self.write_agents(rows, mask)
 
     def get_neighbours_in_radius_batch(self, radii, positions):
         C = self._C
