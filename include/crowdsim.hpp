@@ -54,6 +54,16 @@ inline cs_agent_view agent_view_of(const Agent& a) {
   v.eyesight_range = a.eyesight_range;
   return v;
 }
+// ... and the Agent of one record that a read returned (cs_read_agents, cs_read_agents_by_id)
+inline Agent agent_of_view(const cs_agent_view& v) {
+  Agent a;
+  a.agent_id = v.id;
+  a.position = {v.x, v.y};
+  a.velocity = {v.vx, v.vy};
+  a.next_waypoint = v.next_waypoint;
+  a.eyesight_range = v.eyesight_range;
+  return a;
+}
 constexpr uint32_t kWriteAll = CS_WRITE_POSITION | CS_WRITE_VELOCITY | CS_WRITE_NEXT_WAYPOINT;
 
 struct EventListener {  // lib.rs:22-33
@@ -344,6 +354,26 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     for (const Agent& a : edited) v.push_back(agent_view_of(a));
     write_agents(v, fields);
   }
+  // agents.get(&id) (lib.rs:71) for a batch: the agents with these ids, in the order asked, without reading the rest of
+  // the crowd.  found == nullptr: an id that is not a live agent throws ("unknown agent id").  Otherwise (*found)[k]
+  // says whether ids[k] is alive, and a missing agent's entry is zero except for its id.  A read changes nothing.
+  std::vector<Agent> read_agents(const std::vector<AgentId>& ids, std::vector<uint8_t>* found = nullptr) {
+    std::vector<cs_agent_view> v(ids.size());
+    if (found) found->assign(ids.size(), 0);
+    const int rc = cs_read_agents_by_id(engine_, ids.data(), ids.size(), v.data(), found ? found->data() : nullptr);
+    if (rc != 0) throw std::runtime_error(cs_last_error(engine_));
+    std::vector<Agent> out;
+    for (const cs_agent_view& r : v) out.push_back(agent_of_view(r));
+    return out;
+  }
+  // remove_agents (lib.rs:176-192) for a batch, in one pass over the crowd: the state, the events and the planner
+  // callbacks of remove_agents(ids[0]) ... remove_agents(ids[n-1]).  All or nothing: an unknown id or an id given twice
+  // throws and removes nothing.
+  void remove_agents(const std::vector<AgentId>& ids) {
+    const int rc = cs_remove_agents(engine_, ids.data(), ids.size());
+    after_mutation();
+    if (rc != 0) throw std::runtime_error(cs_last_error(engine_));
+  }
   void step(std::chrono::duration<double> dur) {  // lib.rs:195-383
     cs_step_report rep;
     int rc = cs_step(engine_, dur.count(), &rep);
@@ -512,6 +542,22 @@ class TiledSimulation {
     std::vector<cs_agent_view> v;
     for (const Agent& a : edited) v.push_back(agent_view_of(a));
     write_agents(v, fields);
+  }
+  // Simulation::read_agents(ids) and remove_agents(ids) on the mesh (collective in the distributed forms: every rank
+  // passes the same ids; the read returns the whole answer on every rank)
+  std::vector<Agent> read_agents(const std::vector<AgentId>& ids, std::vector<uint8_t>* found = nullptr) {
+    std::vector<cs_agent_view> v(ids.size());
+    if (found) found->assign(ids.size(), 0);
+    const int rc = cs_mesh_read_agents_by_id(mesh_, ids.data(), ids.size(), v.data(), found ? found->data() : nullptr);
+    if (rc != 0) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    std::vector<Agent> out;
+    for (const cs_agent_view& r : v) out.push_back(agent_of_view(r));
+    return out;
+  }
+  void remove_agents(const std::vector<AgentId>& ids) {
+    const int rc = cs_mesh_remove_agents(mesh_, ids.data(), ids.size());
+    refresh();
+    if (rc != 0) throw std::runtime_error(cs_mesh_last_error(mesh_));
   }
   void step(std::chrono::duration<double> dur) {  // lib.rs:195-383
     cs_step_report rep;

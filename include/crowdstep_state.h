@@ -1,5 +1,6 @@
 /*
- * crowdstep_state.h — writing the crowd's state between steps (the HIP engine only).
+ * crowdstep_state.h — the crowd's state between steps, by agent id: write, read and remove in batches (the HIP engine
+ * only).
  *
  * The reference's crowd state is a public, mutable map (`pub agents: HashMap<AgentId, Agent>`, lib.rs:71): a host
  * that drives the simulation writes to it directly (an actor teleported by a simulator integration, a robot modelled
@@ -30,6 +31,20 @@
  *   - Steps queued without a report complete first (stream order); if one of them failed, the write returns that Err.
  *   - A write fires no events and leaves the last step report alone.
  * cs_agent_view makes read -> edit -> write a round trip: cs_read_agents, change the fields, cs_write_agents.
+ *
+ * Reading and removing by id ("Reading and removing agents by id"): the other two uses of the map,
+ * `agents.get(&id)` and `remove_agents(id)` (lib.rs:176-192), for a batch of ids at once.  One pass over the slots
+ * matches the whole batch; the cost of a call does not grow with the columns of the crowd (the read) or with one scan
+ * and one wait per id (the remove).
+ *   - cs_read_agents_by_id: out[k] is the record cs_read_agents returns for ids[k] at the same moment, byte for byte,
+ *     agents the index never took included.  An id may repeat.  A read changes nothing: the next step runs exactly as
+ *     it would have.
+ *   - cs_remove_agents: leaves the engine in the state cs_remove_agent(ids[0]) ... cs_remove_agent(ids[n-1]) leave it
+ *     in: the same agents gone, the same DESTROYED events and planner remove_agent callbacks in the order of the batch.
+ *     All or nothing: an id that is not a live agent ("unknown agent id", 2) or an id given twice (3) refuses the
+ *     batch with nothing removed, no event, no callback, and the engine not poisoned.
+ *   - Both: external ids under CS_CFG_WIDE_IDS; queued steps complete first and a failure of one of them is returned;
+ *     on a tile engine whose arrays hold ghosts only owned agents match; n == 0 is Ok.
  */
 #ifndef CROWDSTEP_STATE_H
 #define CROWDSTEP_STATE_H
@@ -50,6 +65,19 @@ int cs_write_agents(cs_engine*, const cs_agent_view* in, size_t n, uint32_t fiel
 /* The same on a mesh.  Collective: every rank passes the same batch.  An agent written into a cell another tile owns
  * moves there (the record format of cs_tile_export).  A refused batch fails on every rank, with nothing applied. */
 int cs_mesh_write_agents(cs_mesh*, const cs_agent_view* in, size_t n, uint32_t fields);
+
+
+/* `agents.get(&id)` for n ids at once (lib.rs:71).  out[k] answers ids[k], in the order asked.
+ * found == NULL: every id must be a live agent, else Err "unknown agent id" (2) and out is not written.
+ * found != NULL: found[k] = 1 / 0; for a missing id out[k] is all zero except out[k].id = ids[k]; returns 0. */
+int cs_read_agents_by_id(cs_engine*, const uint64_t* ids, size_t n, cs_agent_view* out, uint8_t* found);
+/* `remove_agents(id)` (lib.rs:176-192) for n ids at once, all or nothing. */
+int cs_remove_agents(cs_engine*, const uint64_t* ids, size_t n);
+/* The same on a mesh.  Collective: every rank passes the same batch and gets the same answer (the read returns the
+ * whole batch on every rank, as cs_mesh_read_agents returns the whole crowd).  The number of collectives does not
+ * depend on n.  A refused batch fails on every rank, with nothing removed. */
+int cs_mesh_read_agents_by_id(cs_mesh*, const uint64_t* ids, size_t n, cs_agent_view* out, uint8_t* found);
+int cs_mesh_remove_agents(cs_mesh*, const uint64_t* ids, size_t n);
 
 #ifdef __cplusplus
 }

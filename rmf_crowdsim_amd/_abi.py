@@ -254,6 +254,12 @@ CS_WRITE_ALL = CS_WRITE_POSITION | CS_WRITE_VELOCITY | CS_WRITE_NEXT_WAYPOINT
 STATE_SYMBOLS = {
     "cs_write_agents": (C.c_int, [C.c_void_p, C.POINTER(AgentView), C.c_size_t, C.c_uint32]),
     "cs_mesh_write_agents": (C.c_int, [C.c_void_p, C.POINTER(AgentView), C.c_size_t, C.c_uint32]),
+    "cs_read_agents_by_id": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(AgentView),
+                                        C.POINTER(C.c_uint8)]),
+    "cs_remove_agents": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t]),
+    "cs_mesh_read_agents_by_id": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(AgentView),
+                                             C.POINTER(C.c_uint8)]),
+    "cs_mesh_remove_agents": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t]),
 }
 
 

@@ -227,13 +227,9 @@ int write_prepare(cs_engine* e, const cs_agent_view* in, size_t n, uint32_t fiel
   return 0;
 }
 
-int write_scratch(cs_engine* e, WritePlan* p) {
-  const size_t n = p->keys.size();
-  auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
-  const size_t b_keys = up(n * sizeof(uint32_t)), b_recs = up(n * sizeof(WriteRec)), b_slot = up(n * sizeof(uint32_t));
-  const size_t b_words = up((n + 1) * sizeof(uint32_t)), b_nmov = 256u;
-  const size_t b_mov = p->any_mover ? up(n * sizeof(HaloRecord)) : 0u;
-  const size_t need = b_keys + b_recs + b_slot + b_words + b_nmov + b_mov;
+// the engine's scratch for calls that address agents by id (the write, and the batched read and remove of
+// cs_agents_by_id.hip.inc): grown as needed, never shrunk
+int write_scratch_reserve(cs_engine* e, size_t need) {
   if (need > e->write_scratch_bytes) {
     if (e->write_scratch) {
       if (hipStreamSynchronize(e->stream) != hipSuccess) {
@@ -251,6 +247,17 @@ int write_scratch(cs_engine* e, WritePlan* p) {
     }
     e->write_scratch_bytes = grow;
   }
+  return 0;
+}
+
+int write_scratch(cs_engine* e, WritePlan* p) {
+  const size_t n = p->keys.size();
+  auto up = [](size_t b) { return (b + 255u) & ~(size_t)255u; };
+  const size_t b_keys = up(n * sizeof(uint32_t)), b_recs = up(n * sizeof(WriteRec)), b_slot = up(n * sizeof(uint32_t));
+  const size_t b_words = up((n + 1) * sizeof(uint32_t)), b_nmov = 256u;
+  const size_t b_mov = p->any_mover ? up(n * sizeof(HaloRecord)) : 0u;
+  const size_t need = b_keys + b_recs + b_slot + b_words + b_nmov + b_mov;
+  if (int rc = write_scratch_reserve(e, need)) return rc;
   unsigned char* s = static_cast<unsigned char*>(e->write_scratch);
   p->d_keys = reinterpret_cast<uint32_t*>(s);
   p->d_recs = reinterpret_cast<WriteRec*>(s + b_keys);
@@ -259,6 +266,35 @@ int write_scratch(cs_engine* e, WritePlan* p) {
   p->d_nmov = reinterpret_cast<uint32_t*>(s + b_keys + b_recs + b_slot + b_words);
   p->d_movers = b_mov ? reinterpret_cast<HaloRecord*>(s + b_keys + b_recs + b_slot + b_words + b_nmov) : nullptr;
   return 0;
+}
+
+// K_match of `n` ascending keys against the slots of buf[cur], on the engine's stream (shared with the batched read and
+// remove, cs_agents_by_id.hip.inc).  d_slot (and meta_dev, when given) start at 0xFFFFFFFF, *d_count at 0.
+void write_launch_match(cs_engine* e, const uint32_t* d_keys, size_t n, uint32_t* d_slot, uint32_t* meta_dev, uint32_t* d_count) {
+  const uint32_t owned_only = (e->tile && e->ghosts_present) ? 1u : 0u;
+  bool staged = n <= WRITE_STAGED_KEYS_MAX;
+  const size_t lds = n * sizeof(uint32_t);
+  if (staged && lds > 64u * 1024u &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k_write_match<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)WRITE_LDS_BYTES) != hipSuccess) {
+    (void)hipGetLastError();
+    staged = false;  // (search in global memory instead)
+  }
+  if (staged) {
+    int n_cu = 0;
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || n_cu <= 0) n_cu = 256;
+    // (one staging per workgroup: a few workgroups per CU stride over all slots)
+    const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, WRITE_LDS_BYTES / std::max<size_t>(lds, 1)));
+    const uint32_t blocks = (uint32_t)std::max<uint64_t>(
+        1, std::min<uint64_t>((e->n_slots + WRITE_STAGED_BLOCK - 1u) / WRITE_STAGED_BLOCK, (uint64_t)n_cu * per_cu));
+    hipLaunchKernelGGL(k_write_match<true>, dim3(blocks), dim3(WRITE_STAGED_BLOCK), lds, e->stream, e->gdev, e->buf[e->cur],
+                       e->n_slots, e->ctr, e->tile ? 1u : 0u, owned_only, d_keys, (uint32_t)n, d_slot, meta_dev,
+                       d_count);
+  } else {
+    hipLaunchKernelGGL(k_write_match<false>, dim3((e->n_slots + WRITE_MATCH_BLOCK - 1u) / WRITE_MATCH_BLOCK),
+                       dim3(WRITE_MATCH_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots, e->ctr,
+                       e->tile ? 1u : 0u, owned_only, d_keys, (uint32_t)n, d_slot, meta_dev, d_count);
+  }
 }
 
 // The queued steps first (stream order), then upload, K_match and the one read back.  Changes nothing on the device
@@ -286,31 +322,7 @@ int write_match(cs_engine* e, WritePlan* p) {
     if (want_meta) HIP_OK_E(e, hipMemsetAsync(p->d_words + 1, 0xFF, n * sizeof(uint32_t), e->stream));
     HIP_OK_E(e, hipStreamSynchronize(e->stream));  // (the host staging dies here)
   }
-  const uint32_t owned_only = (e->tile && e->ghosts_present) ? 1u : 0u;
-  uint32_t* meta_dev = want_meta ? p->d_words + 1 : nullptr;
-  bool staged = n <= WRITE_STAGED_KEYS_MAX;
-  const size_t lds = n * sizeof(uint32_t);
-  if (staged && lds > 64u * 1024u &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(k_write_match<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)WRITE_LDS_BYTES) != hipSuccess) {
-    (void)hipGetLastError();
-    staged = false;  // (search in global memory instead)
-  }
-  if (staged) {
-    int n_cu = 0;
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || n_cu <= 0) n_cu = 256;
-    // (one staging per workgroup: a few workgroups per CU stride over all slots)
-    const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, WRITE_LDS_BYTES / std::max<size_t>(lds, 1)));
-    const uint32_t blocks = (uint32_t)std::max<uint64_t>(
-        1, std::min<uint64_t>((e->n_slots + WRITE_STAGED_BLOCK - 1u) / WRITE_STAGED_BLOCK, (uint64_t)n_cu * per_cu));
-    hipLaunchKernelGGL(k_write_match<true>, dim3(blocks), dim3(WRITE_STAGED_BLOCK), lds, e->stream, e->gdev, e->buf[e->cur],
-                       e->n_slots, e->ctr, e->tile ? 1u : 0u, owned_only, p->d_keys, (uint32_t)n, p->d_slot, meta_dev,
-                       p->d_words);
-  } else {
-    hipLaunchKernelGGL(k_write_match<false>, dim3((e->n_slots + WRITE_MATCH_BLOCK - 1u) / WRITE_MATCH_BLOCK),
-                       dim3(WRITE_MATCH_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots, e->ctr,
-                       e->tile ? 1u : 0u, owned_only, p->d_keys, (uint32_t)n, p->d_slot, meta_dev, p->d_words);
-  }
+  write_launch_match(e, p->d_keys, n, p->d_slot, want_meta ? p->d_words + 1 : nullptr, p->d_words);
   HIP_OK_E(e, hipGetLastError());
   std::vector<uint32_t> words(want_meta ? n + 1 : 1);
   HIP_OK_E(e, hipMemcpyAsync(words.data(), p->d_words, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));

@@ -2699,6 +2699,7 @@ struct cs_engine {
     b += route_desc_cap * sizeof(uint2) + route_xy_cap * sizeof(double) + (uint64_t)route_book_size * sizeof(RouteBookEntry) +
          hlp_scale_cap * sizeof(double) + route_pending_cap * sizeof(uint2);
     for (const Snapshot& sn : snap) b += sn.cap * sizeof(cs_snapshot_record);
+    b += write_scratch_bytes;  // the batches of the by-id calls (write, read, remove)
     return b;
   }
 
@@ -2708,6 +2709,7 @@ struct cs_engine {
     return rebuild();
   }
 
-  void* write_scratch = nullptr;  // device scratch of cs_write_agents (grown as needed, never shrunk: cs_agent_write.hip.inc)
+  void* write_scratch = nullptr;  // device scratch of the by-id calls: cs_write_agents, cs_read_agents_by_id, cs_remove_agents
+                                  // (grown as needed, never shrunk: cs_agent_write.hip.inc)
   size_t write_scratch_bytes = 0;
 };

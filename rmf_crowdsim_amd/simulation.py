@@ -429,6 +429,35 @@ def write_records(records):
     return np.ascontiguousarray(arr.reshape(-1))
 
 
+def id_batch(ids):
+    """`ids` as a contiguous uint64 array (agent ids, in the order given)."""
+    arr = np.asarray(ids)
+    if arr.size and arr.dtype.kind not in "ui":
+        raise CrowdSimError("agent ids must be integers")
+    if arr.size and arr.dtype.kind == "i" and (arr < 0).any():
+        raise CrowdSimError("agent ids must not be negative")
+    return np.ascontiguousarray(arr.reshape(-1), dtype=np.uint64)
+
+
+def state_fn(lib, backend, symbol, what):
+    """An entry point of include/crowdstep_state.h, or the error of a library without that header (the oracle)."""
+    fn = getattr(lib, symbol, None)
+    if fn is None:
+        raise CrowdSimError(f"{what} needs the HIP engine: the {backend} library does not implement "
+                            "include/crowdstep_state.h")
+    return fn
+
+
+def read_by_id(fn, handle, ids, missing_ok):
+    """cs_read_agents_by_id / cs_mesh_read_agents_by_id -> (rc, records, found mask or None)"""
+    keys = id_batch(ids)
+    out = np.zeros(len(keys), dtype=AGENT_DTYPE)
+    found = np.zeros(len(keys), dtype=np.uint8) if missing_ok else None
+    rc = fn(handle, keys.ctypes.data_as(C.POINTER(C.c_uint64)), len(keys), out.ctypes.data_as(C.POINTER(_abi.AgentView)),
+            found.ctypes.data_as(C.POINTER(C.c_uint8)) if missing_ok else None)
+    return rc, out, (found.astype(bool) if missing_ok else None)
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -689,6 +718,30 @@ class Simulation:
         if rc != 0:
             raise self._err()
         return len(arr)
+
+    def read_agents_by_id(self, ids, missing_ok=False):
+        """`agents.get(&id)` (lib.rs:71) for a batch: the rows of read_agents() with these ids, in the order asked (an
+        id may repeat), without reading the rest of the crowd.  missing_ok=False: an id that is not a live agent raises
+        CrowdSimError ("unknown agent id").  missing_ok=True: returns (records, found) with `found` a bool mask; the
+        record of a missing id is zero except for its id.  A read changes nothing (include/crowdstep_state.h)."""
+        fn = state_fn(self._lib, self.backend, "cs_read_agents_by_id", "read_agents_by_id")
+        rc, out, found = read_by_id(fn, self._engine, ids, missing_ok)
+        if rc != 0:
+            raise self._err()
+        return (out, found) if missing_ok else out
+
+    def remove_agents_by_id(self, ids):
+        """`remove_agents(id)` (lib.rs:176-192) for a batch, in one pass over the crowd: the state, the events and the
+        planner callbacks are those of remove_agents(ids[0]) ... remove_agents(ids[-1]).  All or nothing: an unknown id
+        or an id given twice raises CrowdSimError and removes nothing.  Returns the number of agents removed."""
+        fn = state_fn(self._lib, self.backend, "cs_remove_agents", "remove_agents_by_id")
+        keys = id_batch(ids)
+        rc = fn(self._engine, keys.ctypes.data_as(C.POINTER(C.c_uint64)), len(keys))
+        self._agents_cache = None
+        self._dispatch_events()
+        if rc != 0:
+            raise self._err()
+        return len(keys)
 
     def commit_agents(self):
         """Write back the entries of `agents` whose position, velocity or next_waypoint were edited since they were

@@ -665,6 +665,29 @@ class NativeTileMesh:
             raise self._err()
         return len(arr)
 
+    def read_agents_by_id(self, ids, missing_ok=False):
+        """Simulation.read_agents_by_id on the mesh (cs_mesh_read_agents_by_id).  Collective in the distributed form:
+        every rank passes the same ids and gets the whole answer."""
+        from .simulation import read_by_id, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_read_agents_by_id", "read_agents_by_id")
+        rc, out, found = read_by_id(fn, self._mesh, ids, missing_ok)
+        if rc != 0:
+            raise self._err()
+        return (out, found) if missing_ok else out
+
+    def remove_agents_by_id(self, ids):
+        """Simulation.remove_agents_by_id on the mesh (cs_mesh_remove_agents), all or nothing on every tile.  Collective
+        in the distributed form: every rank passes the same ids."""
+        from .simulation import id_batch, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_remove_agents", "remove_agents_by_id")
+        keys = id_batch(ids)
+        rc = fn(self._mesh, keys.ctypes.data_as(self._C.POINTER(self._C.c_uint64)), len(keys))
+        self._agents_cache = None
+        self._dispatch()
+        if rc != 0:
+            raise self._err()
+        return len(keys)
+
     def commit_agents(self):
         """Simulation.commit_agents on the mesh (collective in the distributed form)."""
         from .simulation import edited_agents
