@@ -374,6 +374,22 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     after_mutation();
     if (rc != 0) throw std::runtime_error(cs_last_error(engine_));
   }
+  // planner.set_target(&agents[&id], goal, tolerance) (rmf/mod.rs:217-236) for a batch, in the order of the batch, on the
+  // planner of each agent: a RouteFollower plans the first entry of every new (start, goal) hash pair and books it for the
+  // rest, a host planner's set_target is called.  Returns one CS_TARGET_* status per entry.  All or nothing: an unknown id
+  // or a non-finite goal throws, with no planner called.
+  std::vector<uint8_t> set_targets(const std::vector<AgentId>& ids, const std::vector<Point>& goals, Vec2f tolerance = {}) {
+    if (goals.size() != ids.size()) throw std::runtime_error("set_targets: one goal per id");
+    std::vector<double> xy;
+    for (const Point& g : goals) {
+      xy.push_back(g.x);
+      xy.push_back(g.y);
+    }
+    std::vector<uint8_t> status(ids.size(), 0);
+    const int rc = cs_set_targets(engine_, ids.data(), xy.data(), ids.size(), tolerance.x, tolerance.y, status.data());
+    if (rc != 0) throw std::runtime_error(cs_last_error(engine_));
+    return status;
+  }
   void step(std::chrono::duration<double> dur) {  // lib.rs:195-383
     cs_step_report rep;
     int rc = cs_step(engine_, dur.count(), &rep);
@@ -558,6 +574,20 @@ class TiledSimulation {
     const int rc = cs_mesh_remove_agents(mesh_, ids.data(), ids.size());
     refresh();
     if (rc != 0) throw std::runtime_error(cs_mesh_last_error(mesh_));
+  }
+  // Simulation::set_targets on the mesh (collective in the distributed forms: every rank passes the same batch and gets
+  // the same statuses; every tile books the routes of the whole batch, so that all tiles number routes alike)
+  std::vector<uint8_t> set_targets(const std::vector<AgentId>& ids, const std::vector<Point>& goals, Vec2f tolerance = {}) {
+    if (goals.size() != ids.size()) throw std::runtime_error("set_targets: one goal per id");
+    std::vector<double> xy;
+    for (const Point& g : goals) {
+      xy.push_back(g.x);
+      xy.push_back(g.y);
+    }
+    std::vector<uint8_t> status(ids.size(), 0);
+    const int rc = cs_mesh_set_targets(mesh_, ids.data(), xy.data(), ids.size(), tolerance.x, tolerance.y, status.data());
+    if (rc != 0) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return status;
   }
   void step(std::chrono::duration<double> dur) {  // lib.rs:195-383
     cs_step_report rep;

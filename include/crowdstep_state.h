@@ -1,6 +1,6 @@
 /*
- * crowdstep_state.h — the crowd's state between steps, by agent id: write, read and remove in batches (the HIP engine
- * only).
+ * crowdstep_state.h — the crowd's state between steps, by agent id: write, read, remove and send to goals in batches
+ * (the HIP engine only).
  *
  * The reference's crowd state is a public, mutable map (`pub agents: HashMap<AgentId, Agent>`, lib.rs:71): a host
  * that drives the simulation writes to it directly (an actor teleported by a simulator integration, a robot modelled
@@ -45,6 +45,31 @@
  *     batch with nothing removed, no event, no callback, and the engine not poisoned.
  *   - Both: external ids under CS_CFG_WIDE_IDS; queued steps complete first and a failure of one of them is returned;
  *     on a tile engine whose arrays hold ghosts only owned agents match; n == 0 is Ok.
+ *
+ * Sending agents to goals ("Sending agents to goals between steps"): the planner half of the same
+ * surface, `planner.set_target(&sim.agents[&id], goal, tol)` (rmf/mod.rs:217-236) as a host calls it for an evacuation,
+ * a shift change, a visitor sent to a room, for a batch of (id, goal) entries at once.
+ *   - cs_set_targets: the result is that of set_target(&agents[&ids[k]], goals[k], tol) made for k = 0 .. n-1 IN THE
+ *     ORDER OF THE BATCH, on the planner of each agent's group.  Order matters for CS_HLP_ROUTE: the first entry of a new
+ *     (SpatialHash(start), SpatialHash(goal)) pair calls route_plan with ITS exact position and goal, later entries of the
+ *     same pair (in this batch or any later one) take that route from the book (rmf/mod.rs:222-233).  Routes are numbered
+ *     in that order.
+ *   - `start` is the agent's position as cs_read_agents reports it at that moment: the device's book lookup and the
+ *     host's planning hash the very same f64 value.
+ *   - The agent's agent_cache entry becomes (route, waypoint 0); velocity, position and next_waypoint are untouched.  The
+ *     tolerance is passed on to CALLBACK planners and ignored by ROUTE (as the reference ignores it).
+ *   - An id may appear more than once: the calls are made in order, so the last entry decides the agent's route while
+ *     earlier ones still plan and book theirs.
+ *   - Agents of source-sinks may be sent too.  Their next_waypoint stays; when they reach the sink's waypoint the step's
+ *     own set_target takes over again, as in the reference.
+ *   - All or nothing, decided before any planner is called: an id that is not a live indexed agent ("unknown agent id",
+ *     2; agents the index never took included, as for the write), a non-finite goal or tolerance, null arrays with n > 0
+ *     (3).  A refused batch calls no route_plan and no callback, leaves the route book as it was and does not poison the
+ *     engine.  n == 0 is Ok.
+ *   - External ids under CS_CFG_WIDE_IDS; the call never renumbers.  Queued steps complete first and a failure of one of
+ *     them is returned.  No events; the last step report is left alone.  On a tile engine an exchange made ahead
+ *     (CS_CFG_TILE_OVERLAP) is void afterwards, as after every other change between steps (route state travels in halo
+ *     records).
  */
 #ifndef CROWDSTEP_STATE_H
 #define CROWDSTEP_STATE_H
@@ -78,6 +103,32 @@ int cs_remove_agents(cs_engine*, const uint64_t* ids, size_t n);
  * depend on n.  A refused batch fails on every rank, with nothing removed. */
 int cs_mesh_read_agents_by_id(cs_mesh*, const uint64_t* ids, size_t n, cs_agent_view* out, uint8_t* found);
 int cs_mesh_remove_agents(cs_mesh*, const uint64_t* ids, size_t n);
+
+/* what happened to entry k of cs_set_targets (the optional out array) */
+#define CS_TARGET_IGNORED   0u /* the agent's planner takes no targets: NONE, CONSTANT, ID_PARITY
+                                  (their set_target does nothing, lib.rs:413-415), or ROUTE without route_plan */
+#define CS_TARGET_BOOKED    1u /* ROUTE: the (start, goal) hash pair was in the route book, be it
+                                  through an earlier entry of this very batch                       */
+#define CS_TARGET_PLANNED   2u /* ROUTE: route_plan was called and its route added to the book      */
+#define CS_TARGET_NO_PATH   3u /* ROUTE: route_plan returned 0, or the engine's route table is full
+                                  (4,194,302 routes); the agent keeps what it had, nothing is booked */
+#define CS_TARGET_FORWARDED 4u /* CALLBACK: the host planner's set_target was called                */
+
+/* `planner.set_target(&agents[&ids[k]], goals[k], tol)` (rmf/mod.rs:217-236) for k = 0 .. n-1, in that order, all or
+ * nothing.  goals_xy holds n (x, y) pairs; out_status (n bytes, CS_TARGET_*) may be NULL. */
+int cs_set_targets(cs_engine*, const uint64_t* ids, const double* goals_xy, size_t n, double tol_x, double tol_y,
+                   uint8_t* out_status);
+/* The same on a mesh.  Collective: every rank passes the same batch and gets the same statuses.  The positions of all
+ * entries are gathered (the number of collectives does not depend on n) and every tile runs the book part for the whole
+ * batch in batch order, so that every tile's book numbers routes alike, assigning only to the agents it owns: route_plan
+ * is called once per tile and new route, as by cs_route_resolve.  CALLBACK planners are called by the owning tile only,
+ * in batch order, and BEFORE the route_plan calls of the batch (one engine interleaves the two kinds in batch order).
+ * A refused batch fails on every rank, with no planner called. */
+int cs_mesh_set_targets(cs_mesh*, const uint64_t* ids, const double* goals_xy, size_t n, double tol_x, double tol_y,
+                        uint8_t* out_status);
+/* How many entries of all cs_set_targets calls on this engine (for a mesh: on this tile, cs_mesh_tile) found their
+ * (start, goal) pair in the device's copy of the route book, so that the host made no lookup for them. */
+uint64_t cs_set_targets_device_hits(cs_engine*);
 
 #ifdef __cplusplus
 }

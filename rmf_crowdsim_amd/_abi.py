@@ -251,6 +251,7 @@ CS_WRITE_POSITION = 1
 CS_WRITE_VELOCITY = 2
 CS_WRITE_NEXT_WAYPOINT = 4
 CS_WRITE_ALL = CS_WRITE_POSITION | CS_WRITE_VELOCITY | CS_WRITE_NEXT_WAYPOINT
+CS_TARGET_IGNORED, CS_TARGET_BOOKED, CS_TARGET_PLANNED, CS_TARGET_NO_PATH, CS_TARGET_FORWARDED = 0, 1, 2, 3, 4
 STATE_SYMBOLS = {
     "cs_write_agents": (C.c_int, [C.c_void_p, C.POINTER(AgentView), C.c_size_t, C.c_uint32]),
     "cs_mesh_write_agents": (C.c_int, [C.c_void_p, C.POINTER(AgentView), C.c_size_t, C.c_uint32]),
@@ -260,6 +261,11 @@ STATE_SYMBOLS = {
     "cs_mesh_read_agents_by_id": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(AgentView),
                                              C.POINTER(C.c_uint8)]),
     "cs_mesh_remove_agents": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t]),
+    "cs_set_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_size_t, C.c_double,
+                                  C.c_double, C.POINTER(C.c_uint8)]),
+    "cs_set_targets_device_hits": (C.c_uint64, [C.c_void_p]),
+    "cs_mesh_set_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_size_t, C.c_double,
+                                       C.c_double, C.POINTER(C.c_uint8)]),
 }
 
 

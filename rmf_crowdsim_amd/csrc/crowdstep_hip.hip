@@ -18,6 +18,7 @@
 //   cs_mesh.hip.inc           a crowd cut into tiles behind one handle (cs_mesh_*)
 //   cs_agent_write.hip.inc    writing agents between steps, by id (include/crowdstep_state.h)
 //   cs_agents_by_id.hip.inc   reading and removing agents by id, a batch at a time (the same header)
+//   cs_set_targets.hip.inc    sending agents to goals by id, a batch at a time (the same header)
 //   this file                 includes + the extern "C" boundary
 //
 // Device state is f32 and CELL-RELATIVE: an agent is (stored cell, offset from
@@ -1245,3 +1246,4 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_mesh.hip.inc"
 #include "cs_agent_write.hip.inc"
 #include "cs_agents_by_id.hip.inc"
+#include "cs_set_targets.hip.inc"

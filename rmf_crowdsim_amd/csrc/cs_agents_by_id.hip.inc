@@ -91,8 +91,12 @@ void ids_prepare(const cs_engine* e, const uint64_t* ids, size_t n, const std::v
 
 // The queued steps first (a failure of one of them is the call's), then one upload of the keys and K_match on the
 // engine's stream.  Nothing is waited for here: the caller queues its own kernel and read back behind the match and
-// synchronises once (b->keys stays alive until then).  `records`: room for the gather's output.
-int ids_match(cs_engine* e, IdBatch* b, bool want_meta, bool records) {
+// synchronises once (b->keys stays alive until then).  `records`: room for the gather's output.  `extra_bytes`: room
+// behind the match's own arrays for the caller's (cs_set_targets.hip.inc), returned in *extra (null where nothing was laid
+// out: no keys or no slots).
+int ids_match(cs_engine* e, IdBatch* b, bool want_meta, bool records, size_t extra_bytes = 0,
+              unsigned char** extra = nullptr) {
+  if (extra) *extra = nullptr;
   if (e->poisoned) {
     e->error = e->poison_error;
     return 1;
@@ -103,8 +107,9 @@ int ids_match(cs_engine* e, IdBatch* b, bool want_meta, bool records) {
   auto up = [](size_t bytes) { return (bytes + 255u) & ~(size_t)255u; };
   const size_t b_keys = up(n * sizeof(uint32_t)), b_slot = b_keys, b_words = up((n + 1) * sizeof(uint32_t));
   const size_t b_recs = records ? up(n * sizeof(AgentRec)) : 0u;
-  if (int rc = write_scratch_reserve(e, b_keys + b_slot + b_words + b_recs)) return rc;
+  if (int rc = write_scratch_reserve(e, b_keys + b_slot + b_words + b_recs + extra_bytes)) return rc;
   unsigned char* s = static_cast<unsigned char*>(e->write_scratch);
+  if (extra) *extra = s + b_keys + b_slot + b_words + b_recs;
   b->d_keys = reinterpret_cast<uint32_t*>(s);
   b->d_slot = reinterpret_cast<uint32_t*>(s + b_keys);
   b->d_words = reinterpret_cast<uint32_t*>(s + b_keys + b_slot);

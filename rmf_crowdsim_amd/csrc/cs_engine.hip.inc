@@ -113,6 +113,7 @@ struct cs_engine {
   bool border_on_aux = false;    // the last step's border launch went to aux_stream
   bool exchanged_ahead = false;  // the recv buffers already hold the halo of the state in buf[cur] (ev_xchg)
   uint64_t n_exchanges_ahead = 0, n_exchanges_ahead_used = 0;  // (cs_kernel_stat)
+  uint64_t n_targets_from_device_book = 0;  // entries of cs_set_targets that k_target_probe answered (cs_set_targets_device_hits)
   // the agents changed behind the step kernel's back: what it packed (and what may already have
   // been exchanged ahead) no longer describes buf[cur]
   void halo_invalidate() {

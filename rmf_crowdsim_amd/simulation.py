@@ -19,6 +19,7 @@ Everything forwards to the C ABI (include/crowdstep.h) of the HIP engine; Rust
 """
 import ctypes as C
 import datetime
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
@@ -267,6 +268,23 @@ class RouteFollower(HighLevelPlanner):
     def __init__(self, plan_route, scale=1.0, arrive=0.1, speed=1.0):
         self.plan_route = plan_route
         self.scale, self.arrive, self.speed = float(scale), float(arrive), float(speed)
+        self._hosts = []  # weak references to the simulations and meshes this planner is registered with
+
+    def _registered_with(self, host):
+        """Called by a Simulation or a NativeTileMesh that has registered this planner with its engine."""
+        hosts = self.__dict__.setdefault("_hosts", [])  # (a subclass may have skipped __init__)
+        if not any(h() is host for h in hosts):
+            hosts.append(weakref.ref(host))
+
+    def set_target(self, agent, point, tolerance=(0.0, 0.0)):
+        """RMFPlanner::set_target (rmf/mod.rs:217-236) as a host calls it: forwards `agent.agent_id` to set_targets of the
+        one simulation or mesh this planner is registered with.  Returns that entry's _abi.CS_TARGET_* status."""
+        hosts = [h() for h in getattr(self, "_hosts", []) if h() is not None]
+        if len(hosts) != 1:
+            raise CrowdSimError(
+                f"RouteFollower.set_target: the planner is registered with {len(hosts)} simulations; it forwards to "
+                "Simulation.set_targets (or NativeTileMesh.set_targets) of exactly one: call that directly")
+        return int(hosts[0].set_targets([int(agent.agent_id)], [point], tolerance)[0])
 
     def _desc(self):
         def plan(_user, sx, sy, gx, gy, out, cap):
@@ -458,6 +476,19 @@ def read_by_id(fn, handle, ids, missing_ok):
     return rc, out, (found.astype(bool) if missing_ok else None)
 
 
+def set_targets_by_id(fn, handle, ids, goals, tolerance):
+    """cs_set_targets / cs_mesh_set_targets -> (rc, status array: one _abi.CS_TARGET_* byte per entry)"""
+    keys = id_batch(ids)
+    xy = np.ascontiguousarray(np.asarray(goals, dtype=np.float64).reshape(-1, 2))
+    if len(xy) != len(keys):
+        raise CrowdSimError(f"set_targets: {len(keys)} ids but {len(xy)} goals")
+    tol = np.asarray(tolerance, dtype=np.float64).reshape(2)
+    status = np.zeros(len(keys), dtype=np.uint8)
+    rc = fn(handle, keys.ctypes.data_as(C.POINTER(C.c_uint64)), xy.ctypes.data_as(C.POINTER(C.c_double)), len(keys),
+            float(tol[0]), float(tol[1]), status.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return rc, status
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -586,6 +617,8 @@ class Simulation:
                 raise self._err()
             self._planner_handles[key] = handle
             self._planners_alive.append(planner)
+            if hasattr(planner, "_registered_with"):
+                planner._registered_with(self)
         return self._planner_handles[key]
 
     def _dispatch_events(self):
@@ -742,6 +775,25 @@ class Simulation:
         if rc != 0:
             raise self._err()
         return len(keys)
+
+    def set_targets(self, ids, goals, tolerance=(0.0, 0.0)):
+        """`planner.set_target(&sim.agents[&id], goal, tolerance)` (rmf/mod.rs:217-236) for a batch, between steps: the
+        calls are made in the order of the batch on the planner of each agent (a RouteFollower plans the first entry of
+        every new (start, goal) hash pair and books it for the rest; a host planner's set_target is called).  `goals`:
+        one (x, y) per id.  Returns one _abi.CS_TARGET_* status per entry (uint8).  All or nothing: an unknown id or a
+        non-finite goal raises CrowdSimError with no planner called (include/crowdstep_state.h)."""
+        fn = state_fn(self._lib, self.backend, "cs_set_targets", "set_targets")
+        rc, status = set_targets_by_id(fn, self._engine, ids, goals, tolerance)
+        if rc != 0:
+            raise self._err()
+        return status
+
+    @property
+    def targets_answered_on_device(self):
+        """Entries of all set_targets calls so far whose (start, goal) pair the device's route book held: the host made
+        no lookup for them (cs_set_targets_device_hits; on a tile of a mesh: NativeTileMesh.tile(k))."""
+        fn = state_fn(self._lib, self.backend, "cs_set_targets_device_hits", "targets_answered_on_device")
+        return int(fn(self._engine))
 
     def commit_agents(self):
         """Write back the entries of `agents` whose position, velocity or next_waypoint were edited since they were

@@ -519,6 +519,8 @@ class NativeTileMesh:
                 raise self._err()
             self._handles[key] = handle
             self._alive.append(planner)
+            if hasattr(planner, "_registered_with"):
+                planner._registered_with(self)
         return self._handles[key]
 
     def _dispatch(self):
@@ -687,6 +689,17 @@ class NativeTileMesh:
         if rc != 0:
             raise self._err()
         return len(keys)
+
+    def set_targets(self, ids, goals, tolerance=(0.0, 0.0)):
+        """Simulation.set_targets on the mesh (cs_mesh_set_targets): every tile books the routes of the whole batch in
+        batch order, so that all tiles number routes alike, and assigns to the agents it owns.  Collective in the
+        distributed form: every rank passes the same batch and gets the same statuses."""
+        from .simulation import set_targets_by_id, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_set_targets", "set_targets")
+        rc, status = set_targets_by_id(fn, self._mesh, ids, goals, tolerance)
+        if rc != 0:
+            raise self._err()
+        return status
 
     def commit_agents(self):
         """Simulation.commit_agents on the mesh (collective in the distributed form)."""
