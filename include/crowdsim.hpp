@@ -11,7 +11,9 @@
 #ifndef CROWDSIM_HPP
 #define CROWDSIM_HPP
 
+#include <algorithm>
 #include <chrono>
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <random>
@@ -331,7 +333,17 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     if (sink == UINT32_MAX) throw std::runtime_error(cs_last_error(engine_));
     return sink;
   }
-  void remove_source_sink(std::size_t id) { cs_remove_source_sink(engine_, (uint32_t)id); }  // lib.rs:164
+  // lib.rs:164: the registry entry goes, the agents it spawned walk on; with_agents: they are removed first (events and
+  // planner callbacks included), the reference's own TODO (lib.rs:165-166)
+  void remove_source_sink(std::size_t id, bool with_agents = false) {
+    if (with_agents) {
+      cs_selection sel{};
+      sel.terms = CS_SEL_SOURCE_SINK;
+      sel.source_sink = (uint32_t)id;
+      remove_selected(sel);
+    }
+    cs_remove_source_sink(engine_, (uint32_t)id);
+  }
   std::size_t add_event_listener(std::shared_ptr<EventListener> l) {                        // lib.rs:171
     listeners_[next_listener_] = std::move(l);
     return next_listener_++;
@@ -389,6 +401,38 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     const int rc = cs_set_targets(engine_, ids.data(), xy.data(), ids.size(), tolerance.x, tolerance.y, status.data());
     if (rc != 0) throw std::runtime_error(cs_last_error(engine_));
     return status;
+  }
+  // sim.agents.values().filter(..) (lib.rs:71) on the device: the ids of the agents a cs_selection selects (an AND of
+  // CS_SEL_* terms judged on the record `agents` holds, in f64; include/crowdstep_state.h), ascending, ready for
+  // read_agents(ids) / remove_agents(ids) / set_targets.  `limit`: at most that many ids (the first ones).  Changes nothing.
+  std::vector<AgentId> select_agents(const cs_selection& sel, std::size_t limit = SIZE_MAX) {
+    std::vector<AgentId> ids(std::min(limit, cs_agent_count(engine_)));
+    const std::size_t n = cs_select_agents(engine_, &sel, ids.data(), ids.size());
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    ids.resize(std::min(n, ids.size()));
+    return ids;
+  }
+  // how many agents each of up to CS_SELECT_MAX selections selects, in one pass over the crowd
+  std::vector<uint64_t> count_agents(const std::vector<cs_selection>& selections) {
+    std::vector<uint64_t> counts(selections.size(), 0);
+    if (cs_count_agents(engine_, selections.data(), selections.size(), counts.data()) != 0)
+      throw std::runtime_error(cs_last_error(engine_));
+    return counts;
+  }
+  // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
+  std::vector<AgentId> remove_selected(const cs_selection& sel) {
+    std::vector<AgentId> ids(cs_agent_count(engine_));
+    const std::size_t n = cs_remove_selected(engine_, &sel, ids.data(), ids.size());
+    after_mutation();
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    ids.resize(std::min(n, ids.size()));
+    return ids;
+  }
+  // the handle a planner was registered under, for cs_selection::hlp / lp (a planner never used here selects nobody)
+  template <class P>
+  uint32_t planner_handle(const std::shared_ptr<P>& p) const {
+    auto it = handles_.find(p.get());
+    return it != handles_.end() ? it->second : 0xFFFFFFFEu;
   }
   void step(std::chrono::duration<double> dur) {  // lib.rs:195-383
     cs_step_report rep;
@@ -536,7 +580,15 @@ class TiledSimulation {
     if (sink == UINT32_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
     return sink;
   }
-  void remove_source_sink(std::size_t id) { cs_mesh_remove_source_sink(mesh_, (uint32_t)id); }  // lib.rs:164
+  void remove_source_sink(std::size_t id, bool with_agents = false) {  // lib.rs:164 (Simulation::remove_source_sink)
+    if (with_agents) {
+      cs_selection sel{};
+      sel.terms = CS_SEL_SOURCE_SINK;
+      sel.source_sink = (uint32_t)id;
+      remove_selected(sel);
+    }
+    cs_mesh_remove_source_sink(mesh_, (uint32_t)id);
+  }
   std::size_t add_event_listener(std::shared_ptr<EventListener> l) {                           // lib.rs:171
     listeners_[next_listener_] = std::move(l);
     cs_mesh_event_recording(mesh_, 1);
@@ -588,6 +640,38 @@ class TiledSimulation {
     const int rc = cs_mesh_set_targets(mesh_, ids.data(), xy.data(), ids.size(), tolerance.x, tolerance.y, status.data());
     if (rc != 0) throw std::runtime_error(cs_mesh_last_error(mesh_));
     return status;
+  }
+  // sim.agents.values().filter(..) (lib.rs:71) on the device: the ids of the agents a cs_selection selects (an AND of
+  // CS_SEL_* terms judged on the record `agents` holds, in f64; include/crowdstep_state.h), ascending, ready for
+  // read_agents(ids) / remove_agents(ids) / set_targets.  `limit`: at most that many ids (the first ones).  Changes nothing.
+  std::vector<AgentId> select_agents(const cs_selection& sel, std::size_t limit = SIZE_MAX) {
+    std::vector<AgentId> ids(std::min(limit, cs_mesh_agent_count(mesh_)));
+    const std::size_t n = cs_mesh_select_agents(mesh_, &sel, ids.data(), ids.size());
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    ids.resize(std::min(n, ids.size()));
+    return ids;
+  }
+  // how many agents each of up to CS_SELECT_MAX selections selects, in one pass over the crowd
+  std::vector<uint64_t> count_agents(const std::vector<cs_selection>& selections) {
+    std::vector<uint64_t> counts(selections.size(), 0);
+    if (cs_mesh_count_agents(mesh_, selections.data(), selections.size(), counts.data()) != 0)
+      throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return counts;
+  }
+  // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
+  std::vector<AgentId> remove_selected(const cs_selection& sel) {
+    std::vector<AgentId> ids(cs_mesh_agent_count(mesh_));
+    const std::size_t n = cs_mesh_remove_selected(mesh_, &sel, ids.data(), ids.size());
+    refresh();
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    ids.resize(std::min(n, ids.size()));
+    return ids;
+  }
+  // the handle a planner was registered under, for cs_selection::hlp / lp (a planner never used here selects nobody)
+  template <class P>
+  uint32_t planner_handle(const std::shared_ptr<P>& p) const {
+    auto it = handles_.find(p.get());
+    return it != handles_.end() ? it->second : 0xFFFFFFFEu;
   }
   void step(std::chrono::duration<double> dur) {  // lib.rs:195-383
     cs_step_report rep;

@@ -1,5 +1,5 @@
 /*
- * crowdstep_state.h — the crowd's state between steps, by agent id: write, read, remove and send to goals in batches
+ * crowdstep_state.h — the crowd's state between steps, by agent id: write, read, remove, send to goals in batches, and select
  * (the HIP engine only).
  *
  * The reference's crowd state is a public, mutable map (`pub agents: HashMap<AgentId, Agent>`, lib.rs:71): a host
@@ -70,6 +70,21 @@
  *     them is returned.  No events; the last step report is left alone.  On a tile engine an exchange made ahead
  *     (CS_CFG_TILE_OVERLAP) is void afterwards, as after every other change between steps (route state travels in halo
  *     records).
+ *
+ * Selecting agents ("Selecting agents between steps"): the fourth use of the map, iterating it with a
+ * condition (`sim.agents.values().filter(..)`), which is how a host gets the ids the calls above start from.
+ *   - A cs_selection is an AND of terms (CS_SEL_*).  Every term is evaluated on the record cs_read_agents returns for
+ *     the agent at that moment: x, y the reported f64 position, vx, vy the f32 velocity widened to f64, all arithmetic and
+ *     comparisons in f64, each product and sum rounded once.  cs_select_agents(sel) is exactly the ids of the records of
+ *     cs_read_agents that satisfy the expressions written next to the CS_SEL_* bits, ascending.  A NaN coordinate or
+ *     velocity fails every comparison it takes part in.
+ *   - Agents the index never took are judged by the same rule on the record cs_read_agents lists for them.  On a tile
+ *     engine whose arrays hold ghosts only owned agents count.
+ *   - Refused with 3 (SIZE_MAX where the result is a count), nothing done, the engine usable: unknown term bits, a NaN in
+ *     a field a set term reads (+-inf are fine), r < 0, null pointers with a non-zero count, more than CS_SELECT_MAX
+ *     selections in one counting call.  Unknown planner or sink handles select nobody, as do x1 <= x0 and wp_hi < wp_lo.
+ *   - Queued steps complete first and a failure of one of them is the call's; external ids under CS_CFG_WIDE_IDS; a
+ *     selection or a count never renumbers and clears no flag of the engine: the next step runs exactly as it would have.
  */
 #ifndef CROWDSTEP_STATE_H
 #define CROWDSTEP_STATE_H
@@ -129,6 +144,40 @@ int cs_mesh_set_targets(cs_mesh*, const uint64_t* ids, const double* goals_xy, s
 /* How many entries of all cs_set_targets calls on this engine (for a mesh: on this tile, cs_mesh_tile) found their
  * (start, goal) pair in the device's copy of the route book, so that the host made no lookup for them. */
 uint64_t cs_set_targets_device_hits(cs_engine*);
+
+/* the terms of a selection (bits of cs_selection::terms, ANDed) */
+#define CS_SEL_RECT         1u  /* x0 <= x < x1  &&  y0 <= y < y1                                   */
+#define CS_SEL_CIRCLE       2u  /* (x-cx)*(x-cx) + (y-cy)*(y-cy) < r*r   (strict, like the index)   */
+#define CS_SEL_SOURCE_SINK  4u  /* spawned by source-sink handle `source_sink`, removed or not;
+                                   UINT32_MAX: the agents no sink spawned (cs_add_agents)            */
+#define CS_SEL_HLP          8u  /* high-level planner handle                                         */
+#define CS_SEL_LP          16u  /* local planner handle                                              */
+#define CS_SEL_WAYPOINT    32u  /* wp_lo <= next_waypoint <= wp_hi                                   */
+#define CS_SEL_SPEED       64u  /* speed_lo*speed_lo <= vx*vx + vy*vy < speed_hi*speed_hi            */
+#define CS_SELECT_MAX 1024u     /* selections in one cs_count_agents call */
+typedef struct cs_selection {
+  uint32_t terms;                 /* CS_SEL_* bits, ANDed; 0 selects every agent */
+  uint32_t source_sink, hlp, lp;
+  double x0, y0, x1, y1;
+  double cx, cy, r;
+  uint64_t wp_lo, wp_hi;
+  double speed_lo, speed_hi;
+} cs_selection;
+
+/* ids of the selected agents, ascending.  Returns the full count and writes min(count, cap) ids (the first ones);
+ * out_ids == NULL or cap == 0: the count only.  SIZE_MAX on error. */
+size_t cs_select_agents(cs_engine*, const cs_selection* sel, uint64_t* out_ids, size_t cap);
+/* out_counts[k] = number of agents selections[k] selects, for n <= CS_SELECT_MAX selections in ONE pass over the crowd:
+ * the occupancy of every door, cabin and zone of a building per step.  0 = Ok. */
+int cs_count_agents(cs_engine*, const cs_selection* selections, size_t n, uint64_t* out_counts);
+/* cs_remove_agents(cs_select_agents(sel)): the same agents gone, the same DESTROYED events and planner callbacks, in
+ * ascending id.  Returns the number removed (and writes up to cap of their ids, optional).  SIZE_MAX on error. */
+size_t cs_remove_selected(cs_engine*, const cs_selection* sel, uint64_t* out_ids, size_t cap);
+/* The same on a mesh.  Collective: every rank passes the same selection(s) and gets the whole answer; the number of
+ * collectives does not depend on the crowd or on the size of the answer. */
+size_t cs_mesh_select_agents(cs_mesh*, const cs_selection* sel, uint64_t* out_ids, size_t cap);
+int cs_mesh_count_agents(cs_mesh*, const cs_selection* selections, size_t n, uint64_t* out_counts);
+size_t cs_mesh_remove_selected(cs_mesh*, const cs_selection* sel, uint64_t* out_ids, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -7,14 +7,14 @@ from ._abi import (CS_CFG_DEFAULT, CS_CFG_DENSE, CS_CFG_FORCE_GATHER, CS_CFG_FOR
                    CS_WRITE_NEXT_WAYPOINT, CS_WRITE_POSITION, CS_WRITE_VELOCITY)
 from .simulation import (Agent, CrowdGenerator, CrowdSimError, EventListener, HighLevelPlanner,
                          IdParityHighLevelPlan, LocalPlanner, LocationHash2D, MonotonicCrowd,
-                         NoHighLevelPlan, NoLocalPlan, PoissonCrowd, RouteFollower, SeededPoissonCrowd, Simulation,
-                         SourceSink, SpatialIndex,
+                         NoHighLevelPlan, NoLocalPlan, PoissonCrowd, RouteFollower, SeededPoissonCrowd, Selection,
+                         Simulation, SourceSink, SpatialIndex,
                          StubHighLevelPlan, Zanlungo)
 
 __all__ = [
     "Agent", "CrowdGenerator", "CrowdSimError", "EventListener", "HighLevelPlanner",
     "IdParityHighLevelPlan", "LocalPlanner", "LocationHash2D", "MonotonicCrowd",
-    "NoHighLevelPlan", "NoLocalPlan", "PoissonCrowd", "RouteFollower", "SeededPoissonCrowd", "Simulation",
+    "NoHighLevelPlan", "NoLocalPlan", "PoissonCrowd", "RouteFollower", "SeededPoissonCrowd", "Selection", "Simulation",
     "SourceSink", "SpatialIndex",
     "StubHighLevelPlan", "Zanlungo", "CS_CFG_DEFAULT", "CS_CFG_DENSE", "CS_CFG_FORCE_GATHER",
     "CS_CFG_FORCE_TILED", "CS_CFG_WIDE_IDS", "CS_WRITE_NEXT_WAYPOINT", "CS_WRITE_POSITION", "CS_WRITE_VELOCITY",

@@ -252,6 +252,19 @@ CS_WRITE_VELOCITY = 2
 CS_WRITE_NEXT_WAYPOINT = 4
 CS_WRITE_ALL = CS_WRITE_POSITION | CS_WRITE_VELOCITY | CS_WRITE_NEXT_WAYPOINT
 CS_TARGET_IGNORED, CS_TARGET_BOOKED, CS_TARGET_PLANNED, CS_TARGET_NO_PATH, CS_TARGET_FORWARDED = 0, 1, 2, 3, 4
+CS_SEL_RECT, CS_SEL_CIRCLE, CS_SEL_SOURCE_SINK, CS_SEL_HLP, CS_SEL_LP, CS_SEL_WAYPOINT, CS_SEL_SPEED = 1, 2, 4, 8, 16, 32, 64
+CS_SELECT_MAX = 1024
+
+
+class Selection(C.Structure):
+    """cs_selection: an AND of CS_SEL_* terms (include/crowdstep_state.h)"""
+    _fields_ = [("terms", C.c_uint32), ("source_sink", C.c_uint32), ("hlp", C.c_uint32), ("lp", C.c_uint32),
+                ("x0", C.c_double), ("y0", C.c_double), ("x1", C.c_double), ("y1", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("r", C.c_double),
+                ("wp_lo", C.c_uint64), ("wp_hi", C.c_uint64),
+                ("speed_lo", C.c_double), ("speed_hi", C.c_double)]
+
+
 STATE_SYMBOLS = {
     "cs_write_agents": (C.c_int, [C.c_void_p, C.POINTER(AgentView), C.c_size_t, C.c_uint32]),
     "cs_mesh_write_agents": (C.c_int, [C.c_void_p, C.POINTER(AgentView), C.c_size_t, C.c_uint32]),
@@ -266,6 +279,12 @@ STATE_SYMBOLS = {
     "cs_set_targets_device_hits": (C.c_uint64, [C.c_void_p]),
     "cs_mesh_set_targets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_size_t, C.c_double,
                                        C.c_double, C.POINTER(C.c_uint8)]),
+    "cs_select_agents": (C.c_size_t, [C.c_void_p, C.POINTER(Selection), C.POINTER(C.c_uint64), C.c_size_t]),
+    "cs_count_agents": (C.c_int, [C.c_void_p, C.POINTER(Selection), C.c_size_t, C.POINTER(C.c_uint64)]),
+    "cs_remove_selected": (C.c_size_t, [C.c_void_p, C.POINTER(Selection), C.POINTER(C.c_uint64), C.c_size_t]),
+    "cs_mesh_select_agents": (C.c_size_t, [C.c_void_p, C.POINTER(Selection), C.POINTER(C.c_uint64), C.c_size_t]),
+    "cs_mesh_count_agents": (C.c_int, [C.c_void_p, C.POINTER(Selection), C.c_size_t, C.POINTER(C.c_uint64)]),
+    "cs_mesh_remove_selected": (C.c_size_t, [C.c_void_p, C.POINTER(Selection), C.POINTER(C.c_uint64), C.c_size_t]),
 }
 
 

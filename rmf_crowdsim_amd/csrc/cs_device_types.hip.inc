@@ -79,6 +79,13 @@ struct GroupDev {
   float vanish2;
 };
 
+// What a selection asks of an agent's planner group (cs_select.hip.inc): the owning source-sink as the HOST group knows it
+// (kept after the sink was removed; 0xFFFFFFFF: no sink, cs_add_agents) and the two planner handles.  A table of its
+// own, so that GroupDev, which the step kernels read, stays as it is.
+struct SelGroupDev {
+  uint32_t sink, hlp, lp;
+};
+
 struct SinkDev {
   double src_x, src_y;  // global, for events
   uint32_t src_cell;    // stored cell of the source point (or CS_INVALID_CELL)

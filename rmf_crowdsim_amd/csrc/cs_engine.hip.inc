@@ -672,6 +672,7 @@ struct cs_engine {
     }
     groups.push_back(HostGroup{hlp, lp, eyesight, sink});
     groups_dirty = true;
+    sel_groups_dirty = true;
     return (uint32_t)groups.size() - 1;
   }
   // Room for one more group (and for a waypoint counter up to n_waypoints): meta holds 65,535 groups and 65,535
@@ -2700,7 +2701,8 @@ struct cs_engine {
     b += route_desc_cap * sizeof(uint2) + route_xy_cap * sizeof(double) + (uint64_t)route_book_size * sizeof(RouteBookEntry) +
          hlp_scale_cap * sizeof(double) + route_pending_cap * sizeof(uint2);
     for (const Snapshot& sn : snap) b += sn.cap * sizeof(cs_snapshot_record);
-    b += write_scratch_bytes;  // the batches of the by-id calls (write, read, remove)
+    b += write_scratch_bytes;  // the batches of the by-id calls (write, read, remove) and the selections' lists
+    b += sel_groups_cap * sizeof(SelGroupDev);
     return b;
   }
 
@@ -2713,4 +2715,9 @@ struct cs_engine {
   void* write_scratch = nullptr;  // device scratch of the by-id calls: cs_write_agents, cs_read_agents_by_id, cs_remove_agents
                                   // (grown as needed, never shrunk: cs_agent_write.hip.inc)
   size_t write_scratch_bytes = 0;
+  // the selections' view of the planner groups (cs_select.hip.inc): refreshed inside a selection when a group was added
+  // since, with a flag of its own, so that a selection leaves groups_dirty and the step's tables alone
+  SelGroupDev* sel_groups_dev = nullptr;
+  size_t sel_groups_cap = 0;
+  bool sel_groups_dirty = true;
 };

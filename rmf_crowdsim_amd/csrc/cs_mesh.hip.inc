@@ -47,6 +47,7 @@ struct cs_mesh {
   struct Limbo {
     cs_agent_view view;
     uint32_t hlp;
+    uint32_t lp;  // (the selections ask for it: cs_select.hip.inc)
   };
   std::vector<Limbo> limbo;
   // CS_CFG_WIDE_IDS: an upper bound of the device ids the tiles have handed out, moved by the same calls on every rank
@@ -694,6 +695,7 @@ int cs_mesh_add_agents(cs_mesh* m, const double* xy, size_t n, uint32_t hlp, uin
     l.view.y = xy[2 * failed->last_failed_add_index + 1];
     l.view.eyesight_range = eyesight;
     l.hlp = hlp;
+    l.lp = lp;
     m->limbo.push_back(l);
   }
   return m->fail(failed, first);

@@ -489,6 +489,97 @@ def set_targets_by_id(fn, handle, ids, goals, tolerance):
     return rc, status
 
 
+NO_SOURCE_SINK = 0xFFFFFFFF  # Selection(source_sink=NO_SOURCE_SINK): the agents no sink spawned (add_agents)
+_NO_HANDLE = 0xFFFFFFFE      # a planner the engine has never seen: it selects nobody
+
+
+class Selection:
+    """A condition on agents, an AND of the terms given (include/crowdstep_state.h, cs_selection); no term: every agent.
+        rect=(x0, y0, x1, y1)       x0 <= x < x1 and y0 <= y < y1
+        circle=(cx, cy, r)          (x-cx)*(x-cx) + (y-cy)*(y-cy) < r*r
+        source_sink=handle          spawned by that source-sink, removed or not; NO_SOURCE_SINK: by none (add_agents)
+        high_level_planner=, local_planner=    the planner object the agents were added with (or its integer handle)
+        waypoint=(lo, hi) or k      lo <= next_waypoint <= hi
+        speed=(lo, hi)              lo*lo <= vx*vx + vy*vy < hi*hi
+    Every term is judged on the record read_agents() returns for the agent, in f64."""
+    __slots__ = ("rect", "circle", "source_sink", "high_level_planner", "local_planner", "waypoint", "speed")
+
+    def __init__(self, rect=None, circle=None, source_sink=None, high_level_planner=None, local_planner=None,
+                 waypoint=None, speed=None):
+        self.rect, self.circle, self.source_sink = rect, circle, source_sink
+        self.high_level_planner, self.local_planner = high_level_planner, local_planner
+        self.waypoint, self.speed = waypoint, speed
+
+    def struct(self, handle_of=None):
+        """The cs_selection of this condition.  handle_of(planner) -> the engine's handle of a planner object, or None
+        if it was never registered there."""
+        sel = _abi.Selection()
+
+        def planner(p):
+            if isinstance(p, (int, np.integer)):
+                return int(p)
+            h = handle_of(p) if handle_of is not None else None
+            return _NO_HANDLE if h is None else int(h)
+        if self.rect is not None:
+            sel.terms |= _abi.CS_SEL_RECT
+            sel.x0, sel.y0, sel.x1, sel.y1 = (float(v) for v in self.rect)
+        if self.circle is not None:
+            sel.terms |= _abi.CS_SEL_CIRCLE
+            sel.cx, sel.cy, sel.r = (float(v) for v in self.circle)
+        if self.source_sink is not None:
+            sel.terms |= _abi.CS_SEL_SOURCE_SINK
+            sel.source_sink = int(self.source_sink)
+        if self.high_level_planner is not None:
+            sel.terms |= _abi.CS_SEL_HLP
+            sel.hlp = planner(self.high_level_planner)
+        if self.local_planner is not None:
+            sel.terms |= _abi.CS_SEL_LP
+            sel.lp = planner(self.local_planner)
+        if self.waypoint is not None:
+            sel.terms |= _abi.CS_SEL_WAYPOINT
+            lo, hi = (self.waypoint, self.waypoint) if isinstance(self.waypoint, (int, np.integer)) else self.waypoint
+            lo, hi = max(int(lo), 0), int(hi)
+            sel.wp_lo, sel.wp_hi = (lo, hi) if hi >= 0 else (1, 0)  # (a negative upper bound: nobody)
+        if self.speed is not None:
+            sel.terms |= _abi.CS_SEL_SPEED
+            sel.speed_lo, sel.speed_hi = (float(v) for v in self.speed)
+        return sel
+
+
+def selection_struct(selection, handle_of):
+    """A Selection, a dict of its keywords or a ready _abi.Selection -> _abi.Selection"""
+    if isinstance(selection, _abi.Selection):
+        return selection
+    if isinstance(selection, dict):
+        selection = Selection(**selection)
+    if not isinstance(selection, Selection):
+        raise CrowdSimError("a selection is a Selection, a dict of its keywords or an _abi.Selection")
+    return selection.struct(handle_of)
+
+
+_SIZE_MAX = C.c_size_t(-1).value
+
+
+def select_ids(fn, handle, sel, cap):
+    """cs_select_agents / cs_remove_selected and their mesh forms, with room for `cap` ids -> (the full count, or None on
+    error; the first min(count, cap) ids as a uint64 array)"""
+    cap = max(int(cap), 0)
+    out = np.empty(max(cap, 1), dtype=np.uint64)
+    got = fn(handle, C.byref(sel), out.ctypes.data_as(C.POINTER(C.c_uint64)), cap)
+    if got == _SIZE_MAX:
+        return None, np.zeros(0, dtype=np.uint64)
+    return got, out[:min(got, cap)].copy()
+
+
+def count_selected(fn, handle, selections, handle_of):
+    """cs_count_agents / cs_mesh_count_agents -> (rc, uint64 counts)"""
+    structs = [selection_struct(s, handle_of) for s in selections]
+    arr = (_abi.Selection * max(len(structs), 1))(*structs)
+    out = np.zeros(len(structs), dtype=np.uint64)
+    rc = fn(handle, arr, len(structs), out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    return rc, out
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -677,8 +768,12 @@ class Simulation:
             self._lib.cs_event_recording(self._engine, 1)
         return handle
 
-    def remove_source_sink(self, handle):
-        """lib.rs:164-168"""
+    def remove_source_sink(self, handle, with_agents=False):
+        """lib.rs:164-168: the registry entry goes and the agents it spawned walk on.  with_agents=True removes those
+        agents first (remove_selected(source_sink=handle), events and planner callbacks included): the reference's own
+        TODO (lib.rs:165-166)."""
+        if with_agents:
+            self.remove_selected(source_sink=int(handle))
         self._lib.cs_remove_source_sink(self._engine, int(handle))
         self._source_sinks.pop(handle, None)
 
@@ -775,6 +870,51 @@ class Simulation:
         if rc != 0:
             raise self._err()
         return len(keys)
+
+    def _selection(self, selection, terms):
+        if selection is not None and any(v is not None for v in terms.values()):
+            raise CrowdSimError("give a Selection or its keywords, not both")
+        return selection_struct(selection if selection is not None else Selection(**terms),
+                                lambda p: self._planner_handles.get(id(p)))
+
+    def select_agents(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
+                      local_planner=None, waypoint=None, speed=None, limit=None):
+        """`sim.agents.values().filter(..)` (lib.rs:71) on the device: the ids of the agents that satisfy every term
+        given (see Selection), ascending, as a uint64 array ready for read_agents_by_id / remove_agents_by_id /
+        set_targets.  `limit`: at most that many ids (the first ones).  A selection changes nothing
+        (include/crowdstep_state.h)."""
+        fn = state_fn(self._lib, self.backend, "cs_select_agents", "select_agents")
+        sel = self._selection(selection, dict(rect=rect, circle=circle, source_sink=source_sink,
+                                              high_level_planner=high_level_planner, local_planner=local_planner,
+                                              waypoint=waypoint, speed=speed))
+        n, ids = select_ids(fn, self._engine, sel, len(self) if limit is None else limit)
+        if n is None:
+            raise self._err()
+        return ids
+
+    def count_agents(self, selections):
+        """How many agents each of up to 1024 selections (Selection objects or dicts of their keywords) selects, in one
+        pass over the crowd: the occupancy of every door, cabin and zone per step.  -> uint64 array."""
+        fn = state_fn(self._lib, self.backend, "cs_count_agents", "count_agents")
+        rc, out = count_selected(fn, self._engine, list(selections), lambda p: self._planner_handles.get(id(p)))
+        if rc != 0:
+            raise self._err()
+        return out
+
+    def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
+                        local_planner=None, waypoint=None, speed=None):
+        """remove_agents_by_id(select_agents(..)) in one call: the same agents gone, the same events and planner
+        callbacks, in ascending id.  Returns the removed ids."""
+        fn = state_fn(self._lib, self.backend, "cs_remove_selected", "remove_selected")
+        sel = self._selection(selection, dict(rect=rect, circle=circle, source_sink=source_sink,
+                                              high_level_planner=high_level_planner, local_planner=local_planner,
+                                              waypoint=waypoint, speed=speed))
+        n, ids = select_ids(fn, self._engine, sel, len(self))
+        self._agents_cache = None
+        self._dispatch_events()
+        if n is None:
+            raise self._err()
+        return ids
 
     def set_targets(self, ids, goals, tolerance=(0.0, 0.0)):
         """`planner.set_target(&sim.agents[&id], goal, tolerance)` (rmf/mod.rs:217-236) for a batch, between steps: the

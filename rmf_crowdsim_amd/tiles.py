@@ -573,7 +573,10 @@ class NativeTileMesh:
             self._lib.cs_mesh_event_recording(self._mesh, 1)
         return handle
 
-    def remove_source_sink(self, handle):
+    def remove_source_sink(self, handle, with_agents=False):
+        """Simulation.remove_source_sink on the mesh; with_agents=True removes the agents the sink spawned first."""
+        if with_agents:
+            self.remove_selected(source_sink=int(handle))
         self._lib.cs_mesh_remove_source_sink(self._mesh, int(handle))
 
     def add_event_listener(self, listener):
@@ -689,6 +692,51 @@ class NativeTileMesh:
         if rc != 0:
             raise self._err()
         return len(keys)
+
+    def _selection(self, selection, terms):
+        from .simulation import CrowdSimError, Selection, selection_struct
+        if selection is not None and any(v is not None for v in terms.values()):
+            raise CrowdSimError("give a Selection or its keywords, not both")
+        return selection_struct(selection if selection is not None else Selection(**terms),
+                                lambda p: self._handles.get(id(p)))
+
+    def select_agents(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
+                      local_planner=None, waypoint=None, speed=None, limit=None):
+        """Simulation.select_agents on the mesh (cs_mesh_select_agents): every tile selects among the agents it owns.
+        Collective in the distributed form: every rank passes the same selection and gets the whole answer."""
+        from .simulation import select_ids, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_select_agents", "select_agents")
+        sel = self._selection(selection, dict(rect=rect, circle=circle, source_sink=source_sink,
+                                              high_level_planner=high_level_planner, local_planner=local_planner,
+                                              waypoint=waypoint, speed=speed))
+        n, ids = select_ids(fn, self._mesh, sel, len(self) if limit is None else limit)
+        if n is None:
+            raise self._err()
+        return ids
+
+    def count_agents(self, selections):
+        """Simulation.count_agents on the mesh (cs_mesh_count_agents; collective in the distributed form)."""
+        from .simulation import count_selected, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_count_agents", "count_agents")
+        rc, out = count_selected(fn, self._mesh, list(selections), lambda p: self._handles.get(id(p)))
+        if rc != 0:
+            raise self._err()
+        return out
+
+    def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
+                        local_planner=None, waypoint=None, speed=None):
+        """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
+        from .simulation import select_ids, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_remove_selected", "remove_selected")
+        sel = self._selection(selection, dict(rect=rect, circle=circle, source_sink=source_sink,
+                                              high_level_planner=high_level_planner, local_planner=local_planner,
+                                              waypoint=waypoint, speed=speed))
+        n, ids = select_ids(fn, self._mesh, sel, len(self))
+        self._agents_cache = None
+        self._dispatch()
+        if n is None:
+            raise self._err()
+        return ids
 
     def set_targets(self, ids, goals, tolerance=(0.0, 0.0)):
         """Simulation.set_targets on the mesh (cs_mesh_set_targets): every tile books the routes of the whole batch in
