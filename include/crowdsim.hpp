@@ -272,6 +272,14 @@ struct SourceSink {  // source_sink.rs:36-60
   double agent_eyesight_range;
 };
 
+// What agent_field returns: per bin (ix, iy) of the raster, at iy * nx + ix, the number of agents and (with velocity) the
+// sums of their velocities; mean flow = sum / count.
+struct AgentField {
+  uint32_t nx = 0, ny = 0;
+  std::vector<uint32_t> count;
+  std::vector<double> sum_vx, sum_vy;  // empty unless velocities were asked for
+};
+
 class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
  public:
   std::unordered_map<AgentId, Agent> agents;  // lib.rs:71, refreshed after every mutating call
@@ -418,6 +426,25 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     if (cs_count_agents(engine_, selections.data(), selections.size(), counts.data()) != 0)
       throw std::runtime_error(cs_last_error(engine_));
     return counts;
+  }
+  // Where the crowd is and which way it flows, as a grid, in one pass over the agents on the device: the raster `desc`
+  // (independent of the simulation's grid; include/crowdstep_state.h), only the agents `filter` selects when one is given.
+  AgentField agent_field(const cs_field_desc& desc, bool velocity = false, const cs_selection* filter = nullptr) {
+    AgentField f;
+    const uint64_t bins = (uint64_t)desc.nx * desc.ny;
+    if (bins >= 1 && bins <= CS_FIELD_MAX_CELLS) {  // (any other raster is refused below, before an output is touched)
+      f.nx = desc.nx;
+      f.ny = desc.ny;
+      f.count.assign((std::size_t)bins, 0u);
+      if (velocity) f.sum_vx.assign((std::size_t)bins, 0.0), f.sum_vy.assign((std::size_t)bins, 0.0);
+    } else {
+      f.count.assign(1, 0u);
+      if (velocity) f.sum_vx.assign(1, 0.0), f.sum_vy.assign(1, 0.0);
+    }
+    if (cs_agent_field(engine_, &desc, filter, f.count.data(), velocity ? f.sum_vx.data() : nullptr,
+        velocity ? f.sum_vy.data() : nullptr) != 0)
+      throw std::runtime_error(cs_last_error(engine_));
+    return f;
   }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
@@ -657,6 +684,25 @@ class TiledSimulation {
     if (cs_mesh_count_agents(mesh_, selections.data(), selections.size(), counts.data()) != 0)
       throw std::runtime_error(cs_mesh_last_error(mesh_));
     return counts;
+  }
+  // Where the crowd is and which way it flows, as a grid, in one pass over the agents on the device: the raster `desc`
+  // (independent of the simulation's grid; include/crowdstep_state.h), only the agents `filter` selects when one is given.
+  AgentField agent_field(const cs_field_desc& desc, bool velocity = false, const cs_selection* filter = nullptr) {
+    AgentField f;
+    const uint64_t bins = (uint64_t)desc.nx * desc.ny;
+    if (bins >= 1 && bins <= CS_FIELD_MAX_CELLS) {  // (any other raster is refused below, before an output is touched)
+      f.nx = desc.nx;
+      f.ny = desc.ny;
+      f.count.assign((std::size_t)bins, 0u);
+      if (velocity) f.sum_vx.assign((std::size_t)bins, 0.0), f.sum_vy.assign((std::size_t)bins, 0.0);
+    } else {
+      f.count.assign(1, 0u);
+      if (velocity) f.sum_vx.assign(1, 0.0), f.sum_vy.assign(1, 0.0);
+    }
+    if (cs_mesh_agent_field(mesh_, &desc, filter, f.count.data(), velocity ? f.sum_vx.data() : nullptr,
+        velocity ? f.sum_vy.data() : nullptr) != 0)
+      throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return f;
   }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {

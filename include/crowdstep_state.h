@@ -1,6 +1,6 @@
 /*
- * crowdstep_state.h — the crowd's state between steps, by agent id: write, read, remove, send to goals in batches, and select
- * (the HIP engine only).
+ * crowdstep_state.h — the crowd's state between steps, by agent id: write, read, remove, send to goals in batches, select,
+ * and rasterise into a grid (the HIP engine only).
  *
  * The reference's crowd state is a public, mutable map (`pub agents: HashMap<AgentId, Agent>`, lib.rs:71): a host
  * that drives the simulation writes to it directly (an actor teleported by a simulator integration, a robot modelled
@@ -85,6 +85,32 @@
  *     selections in one counting call.  Unknown planner or sink handles select nobody, as do x1 <= x0 and wp_hi < wp_lo.
  *   - Queued steps complete first and a failure of one of them is the call's; external ids under CS_CFG_WIDE_IDS; a
  *     selection or a count never renumbers and clears no flag of the engine: the next step runs exactly as it would have.
+ *
+ * Rasterising the crowd ("Rasterising the crowd between steps"): the read every consumer of a crowd
+ * makes every step, where the people are and which way they flow, as a grid: a costmap layer, a density heatmap, level of
+ * service, jam detection.  cs_agent_field costs one pass over the agents whatever the number of bins.
+ *   - The raster is a cs_field_desc: nx * ny bins of cell_w x cell_h from the low corner (x0, y0), independent of the
+ *     simulation's grid.  Every output holds nx * ny values, bin (ix, iy) at iy * nx + ix.
+ *   - An agent is the record cs_read_agents returns for it at that moment: x, y the reported f64 position, vx, vy the f32
+ *     velocity widened to f64.  fx = (x - x0) / cell_w in f64: one subtraction and one correctly rounded division, no
+ *     reciprocal, no contraction.  The agent is inside along x iff 0 <= fx && fx < nx (a NaN or an infinity is outside),
+ *     and then ix = (uint32_t)fx; the same for y with y0, cell_h, ny.  So an agent exactly on x0 is in bin 0, one exactly
+ *     on an inner edge is in the upper bin, one exactly on x0 + nx * cell_w is outside.  An agent outside on either axis,
+ *     or failing `filter` (a cs_selection, judged as for cs_select_agents; NULL: every agent), contributes nothing.
+ *   - out_count[bin] is exact.  out_sum_vx / out_sum_vy[bin] are the f64 sums of the widened velocities of the bin's
+ *     agents, added in any order: a bin without agents is exactly +0.0, a bin with one agent holds its velocity exactly
+ *     (a zero sum has the sign +), a bin with n agents is within n * 2^-52 * sum|v| of the exactly rounded sum (twice the
+ *     bound of recursive summation of n terms in any order).  IEEE propagation holds: an agent with a NaN velocity is
+ *     counted and makes the sums of its bin NaN.
+ *   - An output may be NULL; at least one must be given, and the two sums come together or not at all.  The velocities
+ *     are not loaded when only counts are asked for and the filter has no speed term.
+ *   - Agents the index never took are binned by the same rule on the record cs_read_agents lists for them.  On a tile
+ *     engine whose arrays hold ghosts only owned agents count.
+ *   - Refused with 3, the outputs untouched, the engine or mesh usable: a null description, a non-finite x0, y0, cell_w or
+ *     cell_h, cell_w or cell_h <= 0, nx or ny == 0, nx * ny > CS_FIELD_MAX_CELLS, no output, one sum without the other, a
+ *     filter cs_select_agents refuses.
+ *   - Queued steps complete first and a failure of one of them is the call's; no events; the last step report is left
+ *     alone; nothing is renumbered and no flag of the engine is cleared: the next step runs exactly as it would have.
  */
 #ifndef CROWDSTEP_STATE_H
 #define CROWDSTEP_STATE_H
@@ -178,6 +204,27 @@ size_t cs_remove_selected(cs_engine*, const cs_selection* sel, uint64_t* out_ids
 size_t cs_mesh_select_agents(cs_mesh*, const cs_selection* sel, uint64_t* out_ids, size_t cap);
 int cs_mesh_count_agents(cs_mesh*, const cs_selection* selections, size_t n, uint64_t* out_counts);
 size_t cs_mesh_remove_selected(cs_mesh*, const cs_selection* sel, uint64_t* out_ids, size_t cap);
+
+#define CS_FIELD_MAX_CELLS 4194304u /* nx * ny of one raster */
+typedef struct cs_field_desc {
+  double x0, y0;          /* the low corner of bin (0, 0), world coordinates     */
+  double cell_w, cell_h;  /* bin size, finite and > 0; independent of the grid's */
+  uint32_t nx, ny;        /* bins along x and y, each >= 1                       */
+} cs_field_desc;
+/* Per bin of the raster: the number of agents (out_count) and the f64 sums of their velocities (out_sum_vx, out_sum_vy),
+ * nx * ny values each, bin (ix, iy) at iy * nx + ix, in ONE pass over the crowd.  filter == NULL: every agent.  An output
+ * may be NULL (the sums only together).  0 = Ok. */
+int cs_agent_field(cs_engine*, const cs_field_desc* desc, const cs_selection* filter, uint32_t* out_count,
+                   double* out_sum_vx, double* out_sum_vy);
+/* The same on a mesh.  Collective: every rank passes the same arguments and gets the whole raster, the counts the same
+ * bytes on every rank.  Every tile rasterises the agents it owns; a rank sends, per local tile, the bounding box of the
+ * bins that tile touched and that part of its raster, never a whole raster: what travels does not grow with the crowd,
+ * and the number of collectives depends neither on the raster nor on the crowd.  The parts are added in (rank, local
+ * tile) order on every rank, the agents the index never took last.  A tile that fails makes every rank return Err. */
+int cs_mesh_agent_field(cs_mesh*, const cs_field_desc* desc, const cs_selection* filter, uint32_t* out_count,
+                        double* out_sum_vx, double* out_sum_vy);
+/* Bytes this rank contributed to the gather of the last cs_mesh_agent_field (in one process: what it would have sent). */
+uint64_t cs_mesh_field_gather_bytes(const cs_mesh*);
 
 #ifdef __cplusplus
 }

@@ -254,6 +254,7 @@ CS_WRITE_ALL = CS_WRITE_POSITION | CS_WRITE_VELOCITY | CS_WRITE_NEXT_WAYPOINT
 CS_TARGET_IGNORED, CS_TARGET_BOOKED, CS_TARGET_PLANNED, CS_TARGET_NO_PATH, CS_TARGET_FORWARDED = 0, 1, 2, 3, 4
 CS_SEL_RECT, CS_SEL_CIRCLE, CS_SEL_SOURCE_SINK, CS_SEL_HLP, CS_SEL_LP, CS_SEL_WAYPOINT, CS_SEL_SPEED = 1, 2, 4, 8, 16, 32, 64
 CS_SELECT_MAX = 1024
+CS_FIELD_MAX_CELLS = 4194304
 
 
 class Selection(C.Structure):
@@ -264,6 +265,15 @@ class Selection(C.Structure):
                 ("wp_lo", C.c_uint64), ("wp_hi", C.c_uint64),
                 ("speed_lo", C.c_double), ("speed_hi", C.c_double)]
 
+
+class FieldDesc(C.Structure):
+    """cs_field_desc: the raster of cs_agent_field (include/crowdstep_state.h)"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("cell_w", C.c_double), ("cell_h", C.c_double),
+                ("nx", C.c_uint32), ("ny", C.c_uint32)]
+
+
+_FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
+               C.POINTER(C.c_double)]
 
 STATE_SYMBOLS = {
     "cs_write_agents": (C.c_int, [C.c_void_p, C.POINTER(AgentView), C.c_size_t, C.c_uint32]),
@@ -285,6 +295,9 @@ STATE_SYMBOLS = {
     "cs_mesh_select_agents": (C.c_size_t, [C.c_void_p, C.POINTER(Selection), C.POINTER(C.c_uint64), C.c_size_t]),
     "cs_mesh_count_agents": (C.c_int, [C.c_void_p, C.POINTER(Selection), C.c_size_t, C.POINTER(C.c_uint64)]),
     "cs_mesh_remove_selected": (C.c_size_t, [C.c_void_p, C.POINTER(Selection), C.POINTER(C.c_uint64), C.c_size_t]),
+    "cs_agent_field": (C.c_int, list(_FIELD_ARGS)),
+    "cs_mesh_agent_field": (C.c_int, list(_FIELD_ARGS)),
+    "cs_mesh_field_gather_bytes": (C.c_uint64, [C.c_void_p]),
 }
 
 

@@ -2703,6 +2703,7 @@ struct cs_engine {
     for (const Snapshot& sn : snap) b += sn.cap * sizeof(cs_snapshot_record);
     b += write_scratch_bytes;  // the batches of the by-id calls (write, read, remove) and the selections' lists
     b += sel_groups_cap * sizeof(SelGroupDev);
+    b += field_scratch_bytes;  // the raster of the last cs_agent_field (cs_field.hip.inc)
     return b;
   }
 
@@ -2720,4 +2721,7 @@ struct cs_engine {
   SelGroupDev* sel_groups_dev = nullptr;
   size_t sel_groups_cap = 0;
   bool sel_groups_dirty = true;
+  // the raster of cs_agent_field (cs_field.hip.inc): grown to the largest raster asked for, never shrunk
+  void* field_scratch = nullptr;
+  size_t field_scratch_bytes = 0;
 };

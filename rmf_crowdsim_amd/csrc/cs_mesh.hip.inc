@@ -50,6 +50,7 @@ struct cs_mesh {
     uint32_t lp;  // (the selections ask for it: cs_select.hip.inc)
   };
   std::vector<Limbo> limbo;
+  uint64_t field_gather_bytes = 0;  // what this rank contributed to the gather of the last cs_mesh_agent_field
   // CS_CFG_WIDE_IDS: an upper bound of the device ids the tiles have handed out, moved by the same calls on every rank
   // (adds, and one id per source-sink slot and step), so that every rank decides alike when to renumber (mesh_ids_room)
   uint64_t id_bound = 0;

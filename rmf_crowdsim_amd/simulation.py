@@ -580,6 +580,39 @@ def count_selected(fn, handle, selections, handle_of):
     return rc, out
 
 
+def field_desc(origin, cell, shape):
+    """(x0, y0), a bin size (a scalar or a pair (w, h)) and (ny, nx) -> _abi.FieldDesc"""
+    d = _abi.FieldDesc()
+    d.x0, d.y0 = (float(v) for v in origin)
+    cell = np.asarray(cell, dtype=np.float64).reshape(-1)
+    if len(cell) not in (1, 2):
+        raise CrowdSimError("agent_field: cell is a scalar or a pair (w, h)")
+    d.cell_w, d.cell_h = float(cell[0]), float(cell[-1])
+    ny, nx = (int(v) for v in shape)
+    if not (0 <= nx < 2 ** 32 and 0 <= ny < 2 ** 32):
+        raise CrowdSimError("agent_field: shape is (ny, nx), each below 2^32")
+    d.nx, d.ny = nx, ny
+    return d
+
+
+def field_raster(fn, handle, desc, sel, velocity):
+    """cs_agent_field / cs_mesh_agent_field -> (rc, uint32[ny, nx] counts, float64[ny, nx, 2] sums or None); `sel`: an
+    _abi.Selection or None (every agent)"""
+    bins = int(desc.nx) * int(desc.ny)
+    if not 1 <= bins <= _abi.CS_FIELD_MAX_CELLS:
+        bins = 1  # (the call refuses such a raster before it touches an output)
+    count = np.zeros(bins, dtype=np.uint32)
+    vx = np.zeros(bins, dtype=np.float64) if velocity else None
+    vy = np.zeros(bins, dtype=np.float64) if velocity else None
+    dbl = C.POINTER(C.c_double)
+    rc = fn(handle, C.byref(desc), C.byref(sel) if sel is not None else None, count.ctypes.data_as(C.POINTER(C.c_uint32)),
+            vx.ctypes.data_as(dbl) if velocity else None, vy.ctypes.data_as(dbl) if velocity else None)
+    if rc != 0:
+        return rc, None, None
+    shape = (int(desc.ny), int(desc.nx))
+    return rc, count.reshape(shape), np.stack([vx.reshape(shape), vy.reshape(shape)], axis=-1) if velocity else None
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -900,6 +933,21 @@ class Simulation:
         if rc != 0:
             raise self._err()
         return out
+
+    def agent_field(self, origin, cell, shape, selection=None, velocity=False):
+        """Where the crowd is and which way it flows, as a grid, in one pass over the agents on the device
+        (cs_agent_field): `shape` = (ny, nx) bins of size `cell` (a scalar or a pair (w, h)) from the low corner
+        `origin` = (x0, y0), independent of the simulation's grid.  Returns the number of agents per bin, uint32[ny, nx]
+        and, with velocity=True, also the sums of their velocities, float64[ny, nx, 2] (mean flow = sum / count).
+        `selection` (what count_agents accepts) rasterises only the agents it selects.  An agent is binned by the record
+        read_agents() returns for it: ix = floor((x - x0) / w), in when 0 <= ix < nx (include/crowdstep_state.h).  A
+        raster changes nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_agent_field", "agent_field")
+        sel = None if selection is None else selection_struct(selection, lambda p: self._planner_handles.get(id(p)))
+        rc, count, sums = field_raster(fn, self._engine, field_desc(origin, cell, shape), sel, velocity)
+        if rc != 0:
+            raise self._err()
+        return (count, sums) if velocity else count
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

@@ -723,6 +723,18 @@ class NativeTileMesh:
             raise self._err()
         return out
 
+    def agent_field(self, origin, cell, shape, selection=None, velocity=False):
+        """Simulation.agent_field on the mesh (cs_mesh_agent_field): every tile rasterises the agents it owns and only
+        the part of the raster it touched travels.  Collective in the distributed form: every rank passes the same
+        arguments and gets the whole raster."""
+        from .simulation import field_desc, field_raster, selection_struct, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_agent_field", "agent_field")
+        sel = None if selection is None else selection_struct(selection, lambda p: self._handles.get(id(p)))
+        rc, count, sums = field_raster(fn, self._mesh, field_desc(origin, cell, shape), sel, velocity)
+        if rc != 0:
+            raise self._err()
+        return (count, sums) if velocity else count
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
