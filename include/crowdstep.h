@@ -367,6 +367,11 @@ uint64_t cs_device_bytes(cs_engine*);
 /* CS_CFG_WIDE_IDS: renumberings of the device ids so far, and the host wall time spent inside them (ns) */
 #define CS_STAT_RENUMBERINGS 5u
 #define CS_STAT_RENUMBER_NS 6u
+/* windows (workgroups with agents to step) the window builder listed for the LAST step's neighbour kernel, border
+ * windows included; 0 before the first tiled step.  A sort after that step (a spatial query) clears the count of a list
+ * that is not kept, so read it right behind the step.  With full windows it is the sum over the bands of
+ * ceil(owned agents of the band / 256). */
+#define CS_STAT_WINDOWS_LISTED 7u
 uint64_t cs_kernel_stat(cs_engine*, uint32_t which);
 
 /* ---- measurement (bench.py / rocprof cross-check) ---------------------- */

@@ -20,6 +20,7 @@ CS_STAT_EXCHANGES_AHEAD_USED = 3
 CS_STAT_STEPS_ON_KEPT_WINDOWS = 4
 CS_STAT_RENUMBERINGS = 5
 CS_STAT_RENUMBER_NS = 6
+CS_STAT_WINDOWS_LISTED = 7
 
 CS_HLP_NONE, CS_HLP_CONSTANT, CS_HLP_ID_PARITY, CS_HLP_CALLBACK, CS_HLP_ROUTE = 0, 1, 2, 3, 4
 CS_ROUTE_MAX_WAYPOINTS = 1023

@@ -364,6 +364,10 @@ uint64_t cs_kernel_stat(cs_engine* e, uint32_t which) {
   if (which == CS_STAT_STEPS_ON_KEPT_WINDOWS) return e->n_steps_on_kept_windows;
   if (which == CS_STAT_RENUMBERINGS) return e->n_renumberings;
   if (which == CS_STAT_RENUMBER_NS) return e->renumber_ns;
+  if (which == CS_STAT_WINDOWS_LISTED) {
+    uint64_t n = 0;
+    return e->windows_listed(&n) ? 0 : n;
+  }
   Counters c;
   if (e->read_counters(&c)) return 0;
   switch (which) {

@@ -923,6 +923,17 @@ struct cs_engine {
     return 0;
   }
   uint64_t n_steps_on_kept_windows = 0;
+  // the window counters (both lists) of the list the last step's neighbour kernel walked; null: no tiled step yet
+  const uint32_t* last_windows_count = nullptr;
+  int windows_listed(uint64_t* out) {
+    *out = 0;
+    if (!last_windows_count) return 0;
+    uint32_t cnt[2] = {0, 0};
+    HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(hipMemcpy(cnt, last_windows_count, sizeof cnt, hipMemcpyDeviceToHost));
+    *out = (uint64_t)cnt[0] + cnt[1];
+    return 0;
+  }
   // CS_CHECK_WINDOWS=1 (debugging): before the neighbour kernel runs, the band windows it is about to walk are read back
   // and checked on the host: inside the owned rectangle, within the column bound, and (cover mode) tiling every band
   // exactly once.  A bad list fails the step instead of being launched.
@@ -944,6 +955,12 @@ struct cs_engine {
     if (cnt[0]) HIP_OK(hipMemcpy(d.data(), list_dev, (size_t)cnt[0] * sizeof(BlockDesc), hipMemcpyDeviceToHost));
     const uint32_t ncols = gdev.own_y1 - gdev.own_y0;
     std::vector<std::vector<uint8_t>> seen(n_bands, std::vector<uint8_t>(cover ? ncols : 0u, 0));
+    // the slots every window owns, per owned row (a window of whole cells owns its cells' members): they must tile the
+    // row's owned slots exactly once
+    std::vector<uint32_t> cs((size_t)ncells + 1u);
+    HIP_OK(hipMemcpy(cs.data(), cell_start, ((size_t)ncells + 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t own_rows = gdev.own_x1 - gdev.own_x0;
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> runs(own_rows);
     for (uint32_t k = 0; k < cnt[0]; ++k) {
       const BlockDesc& w = d[k];
       const bool in_rows = w.row0 >= gdev.own_x0 && w.row0 < gdev.own_x1 && (w.row0 - gdev.own_x0) % rows == 0u && w.nrows >= 1u &&
@@ -952,16 +969,57 @@ struct cs_engine {
       // max_cols is allowed there and takes the step kernel's gather path)
       const bool in_cols = w.y0 <= w.y1 && w.y0 >= gdev.own_y0 && w.y1 < gdev.own_y1 &&
                            (w.y1 - w.y0 + 1u <= max_cols || ncols > BAND_LDS_COLS);
-      if (!in_rows || !in_cols || w.count != 0u) {
-        std::snprintf(msg, sizeof msg, "window check: window %u of %u is {row0 %u nrows %u y0 %u y1 %u first %u count %u}; owned rows [%u, %u) columns [%u, %u), %u rows per band, %u columns at most",
-                      k, cnt[0], w.row0, w.nrows, w.y0, w.y1, w.first, w.count, gdev.own_x0, gdev.own_x1, gdev.own_y0, gdev.own_y1, rows, max_cols);
+      // a window cut at agent granularity: plain lists only, one or two rows, a workgroup's agents at most, each row's
+      // slots inside the cells y0 .. y1 of that row, the first and the last of them in columns y0 and y1
+      bool cut_ok = w.cut ? (!cover && w.nrows <= 2u && w.count + w.count1 >= 1u && w.count + w.count1 <= (uint32_t)TILE_THREADS &&
+                             (w.nrows == 2u || w.count1 == 0u))
+                          : (w.count == 0u && w.count1 == 0u);
+      if (in_rows && in_cols && cut_ok && w.cut) {
+        bool at_y0 = false, at_y1 = false;
+        for (uint32_t r = 0; r < w.nrows; ++r) {
+          const uint32_t f = r ? w.first1 : w.first, c = r ? w.count1 : w.count;
+          if (!c) continue;
+          const size_t q = (size_t)(w.row0 + r) * gdev.nx;
+          cut_ok = cut_ok && f >= cs[q + w.y0] && f + c <= cs[q + w.y1 + 1u];
+          at_y0 = at_y0 || (f < cs[q + w.y0 + 1u]);
+          at_y1 = at_y1 || (f + c > cs[q + w.y1]);
+        }
+        cut_ok = cut_ok && at_y0 && at_y1;
+      }
+      if (!in_rows || !in_cols || !cut_ok) {
+        std::snprintf(msg, sizeof msg, "window check: window %u of %u is {row0 %u nrows %u cut %u y0 %u y1 %u first %u count %u first1 %u count1 %u}; owned rows [%u, %u) columns [%u, %u), %u rows per band, %u columns at most",
+                      k, cnt[0], w.row0, (unsigned)w.nrows, (unsigned)w.cut, w.y0, w.y1, w.first, w.count, w.first1, w.count1, gdev.own_x0, gdev.own_x1, gdev.own_y0, gdev.own_y1, rows, max_cols);
         check_windows_error = msg;
         error = check_windows_error.c_str();
         return 7;
       }
+      for (uint32_t r = 0; r < w.nrows; ++r) {
+        const size_t q = (size_t)(w.row0 + r) * gdev.nx;
+        const uint32_t f = w.cut ? (r ? w.first1 : w.first) : cs[q + w.y0];
+        const uint32_t c = w.cut ? (r ? w.count1 : w.count) : cs[q + w.y1 + 1u] - f;
+        if (c) runs[w.row0 + r - gdev.own_x0].push_back({f, f + c});
+      }
       if (cover) {
         std::vector<uint8_t>& band = seen[(w.row0 - gdev.own_x0) / rows];
         for (uint32_t y = w.y0; y <= w.y1; ++y) band[y - gdev.own_y0] += 1;
+      }
+    }
+    // (bands wider than the builder's LDS prefix: windows at quantiles, see above; not checked slot by slot)
+    for (uint32_t r = 0; r < own_rows && ncols <= BAND_LDS_COLS; ++r) {
+      std::sort(runs[r].begin(), runs[r].end());
+      const size_t q = (size_t)(gdev.own_x0 + r) * gdev.nx;
+      uint32_t at = cs[q + gdev.own_y0], bad = 0xFFFFFFFFu;
+      for (const auto& s : runs[r]) {
+        if (s.first != at && bad == 0xFFFFFFFFu) bad = std::min(at, s.first);
+        at = s.second;
+      }
+      if (at != cs[q + gdev.own_y1] && bad == 0xFFFFFFFFu) bad = std::min(at, cs[q + gdev.own_y1]);
+      if (bad != 0xFFFFFFFFu) {
+        std::snprintf(msg, sizeof msg, "window check: the windows' slots of row %u do not tile its owned slots [%u, %u) exactly once (%zu runs, %u windows; first gap or overlap at slot %u)",
+                      gdev.own_x0 + r, cs[q + gdev.own_y0], cs[q + gdev.own_y1], runs[r].size(), cnt[0], bad);
+        check_windows_error = msg;
+        error = check_windows_error.c_str();
+        return 7;
       }
     }
     if (cover)
@@ -2210,6 +2268,7 @@ struct cs_engine {
       prof_end();
     }
     HIP_OK(hipGetLastError());
+    last_windows_count = (tiled && n_slots) ? n_blocks_dev : nullptr;  // (CS_STAT_WINDOWS_LISTED; before the swap below)
     if (builders && check_windows)
       if (int rc = check_window_list(blk_desc_back, n_blocks_back, tile_rows, n_bands, tile_max_cols((uint32_t)h), true, 0xFFFFFFFFu)) return rc;
     if (builders) {  // the launch above has cut the next step's windows into the other array

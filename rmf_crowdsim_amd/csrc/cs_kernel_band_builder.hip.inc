@@ -157,11 +157,14 @@
       k = border ? desc_cap - 1u - k : k;
       BlockDesc d;
       d.row0 = row0;
-      d.nrows = nown;
+      d.nrows = (unsigned short)nown;
+      d.cut = 0;
       d.y0 = g.own_y0 + y0;
       d.y1 = g.own_y0 + y1;
       d.first = 0;
       d.count = 0;
+      d.first1 = 0;
+      d.count1 = 0;
       desc[k] = d;
     }
   };
@@ -178,6 +181,91 @@
     BAND_ARRAY(unsigned short, s_win, BAND_LDS_COLS)
     BAND_ARRAY(unsigned short, s_cls, BAND_LDS_COLS)  // index of window w within its list | 0x8000 (border)
     __shared__ uint32_t s_nw, s_first, s_first_b, s_y0;
+    // Plain windows (cover == 0: cut for this step alone) of bands of one or two rows are cut at AGENT granularity.  The
+    // band's agents in the order (column, row, slot) are dealt out `target` at a time: window k owns the positions
+    // [k * target, (k + 1) * target) of that order, the band's last window the remainder, so every workgroup of the step
+    // kernel but one per band is full.  A run of that order is whole columns, then whole cells of the boundary column,
+    // then single agents of one cell, and is therefore one run of slots in each row (BlockDesc::cut).  Every window is
+    // found on its own, by two searches in the prefix; no chain.  The existing bounds hold: a band in which some such
+    // window would stage more than stage_cap agents or span more than max_cols columns (a sparse band beside dense
+    // rows, a crowd's thin edge) is cut by the greedy rule below as before, whole columns per window.  Windows kept
+    // for several steps (cover != 0) must own cells, not slots, and are cut below as well.
+    const uint32_t n_cut = (total + target - 1u) / max(target, 1u);
+    // (a target beyond a workgroup's lanes, CS_TILE_TARGET: windows walked in chunks, cut below as well)
+    if (!cover && nown <= 2u && staged_prefix && target != 0u && target <= (uint32_t)TILE_THREADS && total != 0u &&
+        n_cut <= BAND_LDS_COLS) {
+      __shared__ uint32_t s_cut_bad;
+      if (threadIdx.x == 0) s_cut_bad = 0u;
+      __syncthreads();
+      // smallest column with s_incl[y] >= v (ncols if none)
+      auto lb_lds = [&](uint32_t v) {
+        uint32_t lo = 0, hi = ncols;
+        while (lo < hi) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (s_incl[mid] >= v) hi = mid; else lo = mid + 1;
+        }
+        return lo;
+      };
+      for (uint32_t k = threadIdx.x; k < n_cut; k += blockDim.x) {
+        const uint32_t p0 = k * target, p1 = min(p0 + target, total);
+        const uint32_t ya = lb_lds(p0 + 1u), yb = lb_lds(p1);  // columns of the first and the last owned agent (< ncols)
+        // what it would stage: the extended columns [ya + hl - h, yb + hl + h], clipped to the prefix
+        const uint32_t yl = ya + hl > h ? ya + hl - h : 0u;
+        const uint32_t yr = min(yb + hl + h, ncols_ext - 1u);
+        const uint32_t staged = s_all[yr] - (yl == 0u ? 0u : s_all[yl - 1u]);
+        if (staged > stage_cap || yb - ya + 1u > max_cols) s_cut_bad = 1u;
+        s_win[k] = (unsigned short)ya;
+        s_end[k] = (unsigned short)yb;
+      }
+      __syncthreads();
+      if (s_cut_bad == 0u) {  // (block-uniform)
+        if (threadIdx.x == 0) {
+          uint32_t nb = 0;
+          if (split)
+            for (uint32_t w = 0; w < n_cut; ++w) {
+              const bool b = is_border(s_win[w], s_end[w]);
+              s_cls[w] = (unsigned short)(b ? (nb | 0x8000u) : (w - nb));
+              nb += b ? 1u : 0u;
+            }
+          s_first = n_cut - nb ? atomicAdd(&n_blocks[0], n_cut - nb) : 0u;
+          s_first_b = nb ? atomicAdd(&n_blocks[1], nb) : 0u;
+        }
+        __syncthreads();
+        // slots of row r in front of band position p, which lies in column y (p == total: y == ncols, the row's end)
+        auto row_slot = [&](uint32_t r, uint32_t p, uint32_t y) {
+          const unsigned long long q = (unsigned long long)(row0 + r) * g.nx + g.own_y0 + y;
+          const uint32_t at = cell_start[q];
+          if (y >= ncols) return at;
+          const uint32_t in_col = p - (y == 0u ? 0u : s_incl[y - 1u]);  // positions of column y in front of p
+          if (nown == 1u) return at + in_col;
+          const uint32_t c0 = cell_start[q - (unsigned long long)r * g.nx + 1u] - cell_start[q - (unsigned long long)r * g.nx];
+          return r == 0u ? at + min(in_col, c0) : at + (in_col > c0 ? in_col - c0 : 0u);
+        };
+        for (uint32_t k = threadIdx.x; k < n_cut; k += blockDim.x) {
+          const uint32_t p0 = k * target, p1 = min(p0 + target, total);
+          const uint32_t ya = s_win[k], yb = s_end[k];
+          const uint32_t ye = p1 < total ? lb_lds(p1 + 1u) : ncols;  // column of the first agent behind the window
+          const bool b = split && (s_cls[k] & 0x8000u) != 0u;
+          uint32_t idx = (b ? s_first_b : s_first) + (split ? (s_cls[k] & 0x7FFFu) : k);
+          if (idx >= list_cap) atomicAdd(&ctr->n_win_dropped, 1u);  // (never, if the host's bound holds)
+          if (idx < list_cap) {
+            idx = b ? desc_cap - 1u - idx : idx;
+            BlockDesc d;
+            d.row0 = row0;
+            d.nrows = (unsigned short)nown;
+            d.cut = 1;
+            d.y0 = g.own_y0 + ya;
+            d.y1 = g.own_y0 + yb;
+            d.first = row_slot(0u, p0, ya);
+            d.count = row_slot(0u, p1, ye) - d.first;
+            d.first1 = nown > 1u ? row_slot(1u, p0, ya) : 0u;
+            d.count1 = nown > 1u ? row_slot(1u, p1, ye) - d.first1 : 0u;
+            desc[idx] = d;
+          }
+        }
+        return;
+      }
+    }
     if (threadIdx.x == 0) s_y0 = ncols;  // first non-empty column, found by its own thread below
     __syncthreads();
     constexpr int NQ = 4;

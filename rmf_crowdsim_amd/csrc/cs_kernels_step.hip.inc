@@ -454,9 +454,16 @@ __global__ void __launch_bounds__(256) k_lp_recommended(StepParams P, AgentArray
 // A workgroup of the tiled kernel owns `nrows` consecutive grid rows x the cells [y0, y1].
 // count != 0: a strip of one row cut at AGENT granularity (first, count <= TILE_THREADS).
 // count == 0: a band window of nrows rows cut at CELL granularity (agents = the cells' members).
+// cut != 0: a band window of one or two rows cut at AGENT granularity (build_band, plain windows): it owns the slots
+// [first, first + count) of row row0 and [first1, first1 + count1) of row row0 + 1 (either may be empty), which need
+// not be whole cells; y0 .. y1 are the columns of its first and last owned agent, the span it stages around.  The rest of
+// a cell it owns only partly is staged like any ghost.
 struct BlockDesc {
-  uint32_t row0, nrows, y0, y1, first, count;
+  uint32_t row0;
+  unsigned short nrows, cut;
+  uint32_t y0, y1, first, count, first1, count1;
 };
+static_assert(sizeof(BlockDesc) == 32, "a descriptor is two 16-byte scalar loads");
 
 __global__ void __launch_bounds__(1024) k_build_blocks(GridDev g, const uint32_t* __restrict__ cell_start,
                                                        BlockDesc* __restrict__ desc, uint32_t desc_cap,
@@ -492,6 +499,8 @@ __global__ void __launch_bounds__(1024) k_build_blocks(GridDev g, const uint32_t
         BlockDesc d;
         d.row0 = R;
         d.nrows = 1;
+        d.cut = 0;
+        d.first1 = d.count1 = 0;
         d.y0 = d.y1 = 0;
         d.first = first + k * TILE_THREADS;
         d.count = min((uint32_t)TILE_THREADS, cnt - k * TILE_THREADS);
@@ -814,7 +823,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
   }
   const int n_rows = (int)(g.ncells / g.nx);
   const int row0 = (int)d.row0, nown = (int)d.nrows;
-  const bool strip = d.count != 0;  // cut at agent granularity (k_build_blocks), else a band window
+  const bool strip = d.count != 0 && !d.cut;  // a one-row strip (k_build_blocks), else a band window
   int ylo, yhi;
   if (strip) {
     const uint32_t c_lo = in.cell[d.first], c_hi = in.cell[d.first + d.count - 1];
@@ -839,6 +848,9 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     if (strip) {
       s_rfirst[0] = d.first;
       s_rpref[1] = d.count;
+    } else if (d.cut) {  // a band window cut at agent granularity: the builder has named the slots (nown <= 2)
+      s_rfirst[r] = r ? d.first1 : d.first;
+      s_rpref[r + 1] = r ? d.count1 : d.count;
     } else {
       const unsigned long long rowbase = (unsigned long long)(row0 + r) * g.nx;
       const uint32_t f = cell_start[rowbase + ylo];

@@ -26,6 +26,7 @@ pub const CS_STAT_EXCHANGES_AHEAD_USED: u32 = 3;
 pub const CS_STAT_STEPS_ON_KEPT_WINDOWS: u32 = 4;
 pub const CS_STAT_RENUMBERINGS: u32 = 5;
 pub const CS_STAT_RENUMBER_NS: u32 = 6;
+pub const CS_STAT_WINDOWS_LISTED: u32 = 7;
 
 pub const CS_HLP_NONE: u32 = 0;
 pub const CS_HLP_CONSTANT: u32 = 1;
