@@ -280,6 +280,14 @@ struct AgentField {
   std::vector<double> sum_vx, sum_vy;  // empty unless velocities were asked for
 };
 
+// What close_pairs returns: `count` pairs of agents are closer than the distance; the first min(count, limit) of them,
+// ascending by (a, b) with a < b, and the left-hand side dx * dx + dy * dy of each.
+struct ClosePairs {
+  uint64_t count = 0;
+  std::vector<cs_id_pair> pairs;
+  std::vector<double> d2;
+};
+
 class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
  public:
   std::unordered_map<AgentId, Agent> agents;  // lib.rs:71, refreshed after every mutating call
@@ -445,6 +453,30 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
         velocity ? f.sum_vy.data() : nullptr) != 0)
       throw std::runtime_error(cs_last_error(engine_));
     return f;
+  }
+  // The pairs of agents closer than `distance` on the device (include/crowdstep_state.h, "Pairs of agents between
+  // steps"): judged in f64 on the positions `agents` holds, every pair once as (a, b) with a < b, ascending.  `a` / `b`:
+  // the two roles of a pair (null: everyone), e.g. a = the robots' local planner, b = null.  `limit`: at most that many
+  // pairs (the first ones); a listing of more than CS_PAIRS_MAX pairs throws, count_close_pairs has no limit.
+  ClosePairs close_pairs(double distance, const cs_selection* a = nullptr, const cs_selection* b = nullptr,
+                         std::size_t limit = SIZE_MAX) {
+    ClosePairs out;
+    out.count = count_close_pairs(distance, a, b);
+    const std::size_t cap = (std::size_t)std::min<uint64_t>(out.count, limit);
+    if (!cap) return out;
+    out.pairs.resize(cap);
+    out.d2.resize(cap);
+    const std::size_t n = cs_close_pairs(engine_, distance, a, b, out.pairs.data(), out.d2.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    out.count = n;
+    out.pairs.resize(std::min(n, cap));
+    out.d2.resize(std::min(n, cap));
+    return out;
+  }
+  uint64_t count_close_pairs(double distance, const cs_selection* a = nullptr, const cs_selection* b = nullptr) {
+    const std::size_t n = cs_close_pairs(engine_, distance, a, b, nullptr, nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return n;
   }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
@@ -703,6 +735,30 @@ class TiledSimulation {
         velocity ? f.sum_vy.data() : nullptr) != 0)
       throw std::runtime_error(cs_mesh_last_error(mesh_));
     return f;
+  }
+  // The pairs of agents closer than `distance` on the device (include/crowdstep_state.h, "Pairs of agents between
+  // steps"): judged in f64 on the positions `agents` holds, every pair once as (a, b) with a < b, ascending.  `a` / `b`:
+  // the two roles of a pair (null: everyone), e.g. a = the robots' local planner, b = null.  `limit`: at most that many
+  // pairs (the first ones); a listing of more than CS_PAIRS_MAX pairs throws, count_close_pairs has no limit.
+  ClosePairs close_pairs(double distance, const cs_selection* a = nullptr, const cs_selection* b = nullptr,
+                         std::size_t limit = SIZE_MAX) {
+    ClosePairs out;
+    out.count = count_close_pairs(distance, a, b);
+    const std::size_t cap = (std::size_t)std::min<uint64_t>(out.count, limit);
+    if (!cap) return out;
+    out.pairs.resize(cap);
+    out.d2.resize(cap);
+    const std::size_t n = cs_mesh_close_pairs(mesh_, distance, a, b, out.pairs.data(), out.d2.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    out.count = n;
+    out.pairs.resize(std::min(n, cap));
+    out.d2.resize(std::min(n, cap));
+    return out;
+  }
+  uint64_t count_close_pairs(double distance, const cs_selection* a = nullptr, const cs_selection* b = nullptr) {
+    const std::size_t n = cs_mesh_close_pairs(mesh_, distance, a, b, nullptr, nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return n;
   }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {

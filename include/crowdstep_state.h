@@ -1,6 +1,6 @@
 /*
  * crowdstep_state.h — the crowd's state between steps, by agent id: write, read, remove, send to goals in batches, select,
- * and rasterise into a grid (the HIP engine only).
+ * rasterise into a grid, and list the pairs of agents within a distance of one another (the HIP engine only).
  *
  * The reference's crowd state is a public, mutable map (`pub agents: HashMap<AgentId, Agent>`, lib.rs:71): a host
  * that drives the simulation writes to it directly (an actor teleported by a simulator integration, a robot modelled
@@ -111,6 +111,42 @@
  *     filter cs_select_agents refuses.
  *   - Queued steps complete first and a failure of one of them is the call's; no events; the last step report is left
  *     alone; nothing is renumbered and no flag of the engine is cleared: the next step runs exactly as it would have.
+ *
+ * Pairs of agents between steps ("Pairs of agents between steps"): the questions about TWO agents,
+ * how many overlap (closer than 2 * agent_radius), which pedestrians are within 0.5 m of a robot the host writes into the
+ * crowd, which pairs were within 1.5 m step after step.  cs_close_pairs answers them on the device from the cell-sorted
+ * arrays; nothing of the crowd comes to the host but the pairs asked for.
+ *   - An agent is the record cs_read_agents returns for it at that moment: x, y the reported f64 position.
+ *   - An agent TAKES PART iff its reported position is finite and inside the grid's own rectangle,
+ *     gx0 <= x && x < gx1 && gy0 <= y && y < gy1, the corners being the f64 values cs_read_agents would report for the
+ *     low corner of cell (0, 0) and of the cell one beyond the last row and the last column: gx0 = offset_x,
+ *     gx1 = offset_x + rows * cell_size with rows = (size_t)(height / cell_size) (the index runs x over that many rows),
+ *     gy0 = offset_y, gy1 = offset_y + stride * cell_size with stride = (size_t)(width / cell_size).  On a tile engine
+ *     and on a mesh the rectangle is the GLOBAL grid's.  So no part take: agents the index never took, agents clamped
+ *     into row or column 0 from below the low edge, agents aliased beyond the row stride, agents with a NaN position.
+ *     The last three are exactly the agents whose stored offset does not lie in the cell they are indexed under, which
+ *     is why the search of ceil(distance / cell_size) + 1 cells each way finds every pair.
+ *   - Two agents p and q that both take part are a PAIR iff dx * dx + dy * dy < distance * distance with dx = x_p - x_q,
+ *     dy = y_p - y_q: f64, every difference, product and sum rounded once (no contraction), the comparison strict like
+ *     the index and CS_SEL_CIRCLE.  The expression is symmetric.  distance = +inf: every two participants are a pair;
+ *     distance = 0: no pair, even for two agents on one point.
+ *   - Roles: sel_a and sel_b are cs_selection values judged exactly as for cs_select_agents, NULL: everyone.  A pair is
+ *     reported iff (A(p) && B(q)) || (A(q) && B(p)).  Robots against everyone: sel_a = the robots' local-planner handle
+ *     (CS_SEL_LP), sel_b = NULL.
+ *   - The answer: every pair once, as (a, b) with a < b (external ids under CS_CFG_WIDE_IDS), in ascending order of
+ *     (a, b).  The call returns the full count and writes the first min(count, cap) pairs; out_d2[k] (optional) is the
+ *     left-hand side of pair k, bit for bit.
+ *   - out_pairs == NULL or cap == 0: the count only, from one pass that materialises nothing, exact whatever its size
+ *     (92,700 agents within reach of one another are more than 2^32 pairs).
+ *   - With cap > 0 a count above CS_PAIRS_MAX is refused (SIZE_MAX, "too many pairs to list", the engine usable): the
+ *     sorted prefix needs every pair materialised.  The device scratch of a listing is kept while it is at most 16 MiB
+ *     (and then part of cs_device_bytes); a larger one is freed before the call returns.
+ *   - Refused with SIZE_MAX, nothing written, the engine or mesh usable: a NaN or negative distance, a selection
+ *     cs_select_agents refuses, out_d2 without out_pairs.
+ *   - Queued steps complete first and a failure of one of them is the call's; no events; the last step report is left
+ *     alone; nothing is renumbered.  The call may sort the arrays by cell, as the spatial queries do: the next step runs
+ *     to the same bytes as on an engine that never made the call.  On a tile engine whose arrays hold ghosts only owned
+ *     agents take part.
  */
 #ifndef CROWDSTEP_STATE_H
 #define CROWDSTEP_STATE_H
@@ -225,6 +261,24 @@ int cs_mesh_agent_field(cs_mesh*, const cs_field_desc* desc, const cs_selection*
                         double* out_sum_vx, double* out_sum_vy);
 /* Bytes this rank contributed to the gather of the last cs_mesh_agent_field (in one process: what it would have sent). */
 uint64_t cs_mesh_field_gather_bytes(const cs_mesh*);
+
+#define CS_PAIRS_MAX (1u << 26) /* pairs one listing may hold */
+typedef struct cs_id_pair { uint64_t a, b; } cs_id_pair;   /* a < b */
+/* The pairs of agents closer than `distance`, ascending by (a, b).  Returns the full count and writes min(count, cap)
+ * pairs (the first ones) and, if asked, their squared distances; out_pairs == NULL or cap == 0: the count only (64-bit
+ * on the device, no limit).  sel_a / sel_b: the two roles of a pair, NULL: everyone.  SIZE_MAX on error. */
+size_t cs_close_pairs(cs_engine*, double distance, const cs_selection* sel_a, const cs_selection* sel_b,
+                      cs_id_pair* out_pairs, double* out_d2, size_t cap);
+/* The same on a mesh.  Collective: every rank passes the same arguments and gets the whole answer, byte for byte the
+ * single engine's.  On a mesh of more than one tile `distance` is at most halo_cells * cell_size (so +inf is refused
+ * there, too).  No halo exchange is made for it and the step's own exchange state is left as it is: every tile lists
+ * the pairs among the agents it holds and exports a record (id, position, roles, tile) of each participant within reach
+ * of an edge behind which another tile lies; one gather brings these band records to every rank, each rank tests its
+ * tiles' band agents against the records of the tiles with a higher index (every cross-tile pair exactly once), one more
+ * gather moves the pair lists (the count-only form: the counts), and every rank merges the sorted runs.  The number of
+ * collectives depends neither on the crowd nor on the answer.  A tile that fails makes every rank return SIZE_MAX. */
+size_t cs_mesh_close_pairs(cs_mesh*, double distance, const cs_selection* sel_a, const cs_selection* sel_b,
+                           cs_id_pair* out_pairs, double* out_d2, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -256,6 +256,7 @@ CS_TARGET_IGNORED, CS_TARGET_BOOKED, CS_TARGET_PLANNED, CS_TARGET_NO_PATH, CS_TA
 CS_SEL_RECT, CS_SEL_CIRCLE, CS_SEL_SOURCE_SINK, CS_SEL_HLP, CS_SEL_LP, CS_SEL_WAYPOINT, CS_SEL_SPEED = 1, 2, 4, 8, 16, 32, 64
 CS_SELECT_MAX = 1024
 CS_FIELD_MAX_CELLS = 4194304
+CS_PAIRS_MAX = 1 << 26
 
 
 class Selection(C.Structure):
@@ -273,6 +274,13 @@ class FieldDesc(C.Structure):
                 ("nx", C.c_uint32), ("ny", C.c_uint32)]
 
 
+class IdPair(C.Structure):
+    """cs_id_pair: one pair of cs_close_pairs, a < b (include/crowdstep_state.h)"""
+    _fields_ = [("a", C.c_uint64), ("b", C.c_uint64)]
+
+
+_PAIRS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.POINTER(IdPair), C.POINTER(C.c_double),
+               C.c_size_t]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -299,6 +307,8 @@ STATE_SYMBOLS = {
     "cs_agent_field": (C.c_int, list(_FIELD_ARGS)),
     "cs_mesh_agent_field": (C.c_int, list(_FIELD_ARGS)),
     "cs_mesh_field_gather_bytes": (C.c_uint64, [C.c_void_p]),
+    "cs_close_pairs": (C.c_size_t, list(_PAIRS_ARGS)),
+    "cs_mesh_close_pairs": (C.c_size_t, list(_PAIRS_ARGS)),
 }
 
 

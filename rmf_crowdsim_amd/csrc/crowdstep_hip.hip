@@ -19,6 +19,9 @@
 //   cs_agent_write.hip.inc    writing agents between steps, by id (include/crowdstep_state.h)
 //   cs_agents_by_id.hip.inc   reading and removing agents by id, a batch at a time (the same header)
 //   cs_set_targets.hip.inc    sending agents to goals by id, a batch at a time (the same header)
+//   cs_select.hip.inc         selecting, counting and removing agents by region, owner and state (the same header)
+//   cs_field.hip.inc          rasterising the crowd into a grid (the same header)
+//   cs_close_pairs.hip.inc    the pairs of agents within a distance of one another (the same header)
 //   this file                 includes + the extern "C" boundary
 //
 // Device state is f32 and CELL-RELATIVE: an agent is (stored cell, offset from
@@ -102,7 +105,7 @@ void cs_destroy(cs_engine* e) {
   hipFree(e->route_desc_dev); hipFree(e->route_xy_dev); hipFree(e->route_book_dev); hipFree(e->hlp_scale_dev); hipFree(e->route_pending_dev);
   hipFree(e->groups_dev); hipFree(e->sinks_dev); hipFree(e->waypoints_dev);
   hipFree(e->src_cell_start); hipFree(e->src_sorted); hipFree(e->src_occupied);
-  hipFree(e->want_dev); hipFree(e->spawned_slots_dev); hipFree(e->spawn_scratch); hipHostFree(e->want_host); hipFree(e->blk_desc); hipFree(e->blk_desc_back); hipFree(e->n_blocks_dev); hipFree(e->n_blocks_back); hipFree(e->band_prefix); hipFree(e->tile_spill); hipFree(e->spawn_rec_dev); hipFree(e->find_dev); hipFree(e->step_flags_dev); hipFree(e->query_scratch); hipFree(e->scan_tile_sums); hipFree(e->write_scratch); hipFree(e->sel_groups_dev); hipFree(e->field_scratch);
+  hipFree(e->want_dev); hipFree(e->spawned_slots_dev); hipFree(e->spawn_scratch); hipHostFree(e->want_host); hipFree(e->blk_desc); hipFree(e->blk_desc_back); hipFree(e->n_blocks_dev); hipFree(e->n_blocks_back); hipFree(e->band_prefix); hipFree(e->tile_spill); hipFree(e->spawn_rec_dev); hipFree(e->find_dev); hipFree(e->step_flags_dev); hipFree(e->query_scratch); hipFree(e->scan_tile_sums); hipFree(e->write_scratch); hipFree(e->sel_groups_dev); hipFree(e->field_scratch); hipFree(e->pairs_scratch);
   for (auto& t : e->timed) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
   for (auto ev : e->event_pool) hipEventDestroy(ev);
   if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
@@ -1253,3 +1256,4 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_set_targets.hip.inc"
 #include "cs_select.hip.inc"
 #include "cs_field.hip.inc"
+#include "cs_close_pairs.hip.inc"

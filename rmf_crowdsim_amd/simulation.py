@@ -613,6 +613,39 @@ def field_raster(fn, handle, desc, sel, velocity):
     return rc, count.reshape(shape), np.stack([vx.reshape(shape), vy.reshape(shape)], axis=-1) if velocity else None
 
 
+def close_pairs_call(fn, handle, distance, sel_a, sel_b, cap, distances):
+    """cs_close_pairs / cs_mesh_close_pairs with room for `cap` pairs -> (the full count, or None on error; uint64[n, 2]
+    pairs; float64[n] squared distances or None).  sel_a / sel_b: an _abi.Selection or None (everyone); cap == 0: the
+    count only."""
+    cap = max(int(cap), 0)
+    pairs = np.zeros((max(cap, 1), 2), dtype=np.uint64)
+    d2 = np.zeros(max(cap, 1), dtype=np.float64) if (distances and cap) else None
+    got = fn(handle, float(distance), C.byref(sel_a) if sel_a is not None else None,
+             C.byref(sel_b) if sel_b is not None else None,
+             pairs.ctypes.data_as(C.POINTER(_abi.IdPair)) if cap else None,
+             d2.ctypes.data_as(C.POINTER(C.c_double)) if d2 is not None else None, cap)
+    if got == _SIZE_MAX:
+        return None, np.zeros((0, 2), dtype=np.uint64), None
+    n = min(got, cap)
+    return got, pairs[:n].copy(), (d2[:n].copy() if d2 is not None else (np.zeros(0) if distances else None))
+
+
+def close_pairs_of(fn, handle, handle_of, err, distance, a, b, limit, distances):
+    """close_pairs of Simulation and NativeTileMesh: limit=None lists every pair (one counting call first)"""
+    sel_a = None if a is None else selection_struct(a, handle_of)
+    sel_b = None if b is None else selection_struct(b, handle_of)
+    if limit is None:
+        limit, _, _ = close_pairs_call(fn, handle, distance, sel_a, sel_b, 0, False)
+        if limit is None:
+            raise err()
+        if limit > _abi.CS_PAIRS_MAX:
+            limit = 1  # (the listing is refused by the library, with its message: no room is made for it here)
+    n, pairs, d2 = close_pairs_call(fn, handle, distance, sel_a, sel_b, limit, distances)
+    if n is None:
+        raise err()
+    return (pairs, d2) if distances else pairs
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -948,6 +981,28 @@ class Simulation:
         if rc != 0:
             raise self._err()
         return (count, sums) if velocity else count
+
+    def close_pairs(self, distance, a=None, b=None, *, limit=None, distances=False):
+        """The pairs of agents closer than `distance`, on the device (cs_close_pairs): contacts, overlaps, near misses.
+        Returns a uint64[n, 2] array of (a, b) ids with a < b, every pair once, ascending; with distances=True also the
+        float64[n] left-hand sides dx*dx + dy*dy.  Two agents are a pair iff dx*dx + dy*dy < distance*distance in f64 on
+        the positions read_agents() reports, both inside the grid's rectangle (include/crowdstep_state.h).  `a`, `b`: the
+        two roles of a pair, what select_agents accepts (a Selection, a dict of its keywords, None: everyone); a pair
+        counts iff one of the two is in `a` and the other in `b`.  `limit`: at most that many pairs (the first ones);
+        listing more than _abi.CS_PAIRS_MAX pairs raises, count_close_pairs has no limit.  Changes nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_close_pairs", "close_pairs")
+        return close_pairs_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, a, b,
+                              limit, distances)
+
+    def count_close_pairs(self, distance, a=None, b=None):
+        """len(close_pairs(distance, a, b)) from one pass that lists nothing, exact whatever its size."""
+        fn = state_fn(self._lib, self.backend, "cs_close_pairs", "close_pairs")
+        handle_of = lambda p: self._planner_handles.get(id(p))  # noqa: E731
+        n, _, _ = close_pairs_call(fn, self._engine, distance, None if a is None else selection_struct(a, handle_of),
+                                   None if b is None else selection_struct(b, handle_of), 0, False)
+        if n is None:
+            raise self._err()
+        return int(n)
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

@@ -735,6 +735,27 @@ class NativeTileMesh:
             raise self._err()
         return (count, sums) if velocity else count
 
+    def close_pairs(self, distance, a=None, b=None, *, limit=None, distances=False):
+        """Simulation.close_pairs on the mesh (cs_mesh_close_pairs): the single engine's answer, byte for byte.  On a mesh
+        of more than one tile `distance` is at most halo_cells * cell_size.  Every tile lists the pairs among its own
+        agents; the agents near a cut travel as band records and are paired across tiles; no halo exchange is made.
+        Collective in the distributed form: every rank passes the same arguments and gets the whole answer."""
+        from .simulation import close_pairs_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_close_pairs", "close_pairs")
+        return close_pairs_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, a, b, limit,
+                              distances)
+
+    def count_close_pairs(self, distance, a=None, b=None):
+        """Simulation.count_close_pairs on the mesh (collective in the distributed form): only counts travel."""
+        from .simulation import close_pairs_call, selection_struct, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_close_pairs", "close_pairs")
+        handle_of = lambda p: self._handles.get(id(p))  # noqa: E731
+        n, _, _ = close_pairs_call(fn, self._mesh, distance, None if a is None else selection_struct(a, handle_of),
+                                   None if b is None else selection_struct(b, handle_of), 0, False)
+        if n is None:
+            raise self._err()
+        return int(n)
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
