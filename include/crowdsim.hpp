@@ -288,6 +288,16 @@ struct ClosePairs {
   std::vector<double> d2;
 };
 
+// What agent_clusters returns: the members of the reported clusters ascending by id with the label of each (the smallest
+// id of its cluster), and the clusters ascending by label (size, box and f64 sums of the members' positions).
+struct AgentClusters {
+  std::vector<uint64_t> ids, labels;
+  std::vector<cs_cluster> clusters;
+};
+struct ClusterCounts {
+  uint64_t clusters = 0, agents = 0;
+};
+
 class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
  public:
   std::unordered_map<AgentId, Agent> agents;  // lib.rs:71, refreshed after every mutating call
@@ -477,6 +487,34 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     const std::size_t n = cs_close_pairs(engine_, distance, a, b, nullptr, nullptr, 0);
     if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
     return n;
+  }
+  // Which agents hang together (cs_agent_clusters, include/crowdstep_state.h "Clusters of agents between steps"): the
+  // connected components of the members (`members`, null: everyone) under the links of close_pairs(distance, members,
+  // members), labelled by their smallest id; only clusters of at least min_size members are reported.
+  AgentClusters agent_clusters(double distance, const cs_selection* members = nullptr, uint64_t min_size = 1) {
+    AgentClusters out;
+    const ClusterCounts c = count_clusters(distance, members, min_size);
+    out.ids.resize((std::size_t)c.agents);
+    out.labels.resize((std::size_t)c.agents);
+    out.clusters.resize((std::size_t)c.clusters);
+    std::size_t na = 0, nc = 0;
+    if (cs_agent_clusters(engine_, distance, members, min_size, out.ids.empty() ? nullptr : out.ids.data(),
+                         out.ids.empty() ? nullptr : out.labels.data(), out.ids.size(), &na,
+                         out.clusters.empty() ? nullptr : out.clusters.data(), out.clusters.size(), &nc))
+      throw std::runtime_error(cs_last_error(engine_));
+    out.ids.resize(std::min(na, out.ids.size()));
+    out.labels.resize(out.ids.size());
+    out.clusters.resize(std::min(nc, out.clusters.size()));
+    return out;
+  }
+  ClusterCounts count_clusters(double distance, const cs_selection* members = nullptr, uint64_t min_size = 1) {
+    std::size_t na = 0, nc = 0;
+    if (cs_agent_clusters(engine_, distance, members, min_size, nullptr, nullptr, 0, &na, nullptr, 0, &nc))
+      throw std::runtime_error(cs_last_error(engine_));
+    ClusterCounts c;
+    c.clusters = nc;
+    c.agents = na;
+    return c;
   }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
@@ -759,6 +797,34 @@ class TiledSimulation {
     const std::size_t n = cs_mesh_close_pairs(mesh_, distance, a, b, nullptr, nullptr, 0);
     if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
     return n;
+  }
+  // Which agents hang together (cs_agent_clusters, include/crowdstep_state.h "Clusters of agents between steps"): the
+  // connected components of the members (`members`, null: everyone) under the links of close_pairs(distance, members,
+  // members), labelled by their smallest id; only clusters of at least min_size members are reported.
+  AgentClusters agent_clusters(double distance, const cs_selection* members = nullptr, uint64_t min_size = 1) {
+    AgentClusters out;
+    const ClusterCounts c = count_clusters(distance, members, min_size);
+    out.ids.resize((std::size_t)c.agents);
+    out.labels.resize((std::size_t)c.agents);
+    out.clusters.resize((std::size_t)c.clusters);
+    std::size_t na = 0, nc = 0;
+    if (cs_mesh_agent_clusters(mesh_, distance, members, min_size, out.ids.empty() ? nullptr : out.ids.data(),
+                              out.ids.empty() ? nullptr : out.labels.data(), out.ids.size(), &na,
+                              out.clusters.empty() ? nullptr : out.clusters.data(), out.clusters.size(), &nc))
+      throw std::runtime_error(cs_mesh_last_error(mesh_));
+    out.ids.resize(std::min(na, out.ids.size()));
+    out.labels.resize(out.ids.size());
+    out.clusters.resize(std::min(nc, out.clusters.size()));
+    return out;
+  }
+  ClusterCounts count_clusters(double distance, const cs_selection* members = nullptr, uint64_t min_size = 1) {
+    std::size_t na = 0, nc = 0;
+    if (cs_mesh_agent_clusters(mesh_, distance, members, min_size, nullptr, nullptr, 0, &na, nullptr, 0, &nc))
+      throw std::runtime_error(cs_mesh_last_error(mesh_));
+    ClusterCounts c;
+    c.clusters = nc;
+    c.agents = na;
+    return c;
   }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {

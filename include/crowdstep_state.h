@@ -1,6 +1,7 @@
 /*
  * crowdstep_state.h — the crowd's state between steps, by agent id: write, read, remove, send to goals in batches, select,
- * rasterise into a grid, and list the pairs of agents within a distance of one another (the HIP engine only).
+ * rasterise into a grid, list the pairs of agents within a distance of one another and cluster the agents by that distance
+ * (the HIP engine only).
  *
  * The reference's crowd state is a public, mutable map (`pub agents: HashMap<AgentId, Agent>`, lib.rs:71): a host
  * that drives the simulation writes to it directly (an actor teleported by a simulator integration, a robot modelled
@@ -147,6 +148,42 @@
  *     alone; nothing is renumbered.  The call may sort the arrays by cell, as the spatial queries do: the next step runs
  *     to the same bytes as on an engine that never made the call.  On a tile engine whose arrays hold ghosts only owned
  *     agents take part.
+ *
+ * Clusters of agents between steps ("Clusters of agents between steps"): the question about MANY
+ * agents, which of them hang together: which stalled agents form one jam, how big it is and where, which pedestrians
+ * walk as a group, which blob blocks a corridor, who is in one contact chain.  cs_agent_clusters answers with the
+ * connected components of the graph cs_close_pairs defines, merged on the device; what comes to the host is one label per
+ * agent and 64 bytes per cluster, never a pair.
+ *   - An agent is the record cs_read_agents returns for it at that moment: x, y the reported f64 position.
+ *   - An agent is a MEMBER iff it takes part by the rule of cs_close_pairs (a finite reported position inside the grid's
+ *     own rectangle, gx0 <= x && x < gx1 && gy0 <= y && y < gy1) and satisfies `members`, a cs_selection judged exactly
+ *     as for cs_select_agents, NULL: everyone.  On a tile engine whose arrays hold ghosts only owned agents are members.
+ *     Agents the index never took are no members.
+ *   - Two members p and q are LINKED iff they are a pair of cs_close_pairs(distance, members, members): dx * dx + dy * dy <
+ *     distance * distance with dx = x_p - x_q, dy = y_p - y_q, f64, every difference, product and sum rounded once (no
+ *     contraction, no f32 pre-reject), the comparison strict.
+ *   - A CLUSTER is a connected component of the members under the links.  A member without a link is a cluster of size 1.
+ *     An agent that is no member never bridges two members, however close it stands to both.  distance = 0: every member
+ *     is its own cluster, even two on one point; distance = +inf: all members are one cluster.
+ *   - A cluster's LABEL is the smallest id among its members (external ids under CS_CFG_WIDE_IDS), so it depends neither
+ *     on the order of the slots, nor on tiles, nor on the order in which the device merged.
+ *   - min_size: only clusters with at least min_size members are reported, in both outputs and both counts; 0 and 1 both
+ *     report every cluster.
+ *   - The answer: *n_agents = the members of reported clusters; out_ids gets the first min(*n_agents, agent_cap) of their
+ *     ids, ascending, and out_labels[k] the label of out_ids[k].  *n_clusters = the reported clusters; out_clusters gets
+ *     the first min(*n_clusters, cluster_cap) of them, ascending by label.  Nothing is written beyond those entries.
+ *   - Of a cs_cluster, label, size, min_x, min_y, max_x, max_y (the box of the members' reported positions) are exact.
+ *     sum_x / sum_y are the f64 sums of the members' reported positions, added in any order: a cluster of one member
+ *     holds its position exactly, a cluster of n members is within n * 2^-52 * sum|x| of the exactly rounded sum (the
+ *     bound of cs_agent_field).  The centroid is sum / size.
+ *   - Every pointer among the outputs and the two counts may be NULL (out_ids may be given without out_labels); with all
+ *     of them NULL the call only validates.
+ *   - Refused with 3, nothing written, the engine or mesh usable: a NaN or negative distance, a selection
+ *     cs_select_agents refuses, out_labels without out_ids.
+ *   - Queued steps complete first and a failure of one of them is the call's; no events; the last step report is left
+ *     alone; nothing is renumbered.  The call may sort the arrays by cell, as the spatial queries do: the next step runs
+ *     to the same bytes as on an engine that never made the call.  The device scratch of a call is kept while it is at
+ *     most 16 MiB (the scratch of cs_close_pairs, part of cs_device_bytes); a larger one is freed before the call returns.
  */
 #ifndef CROWDSTEP_STATE_H
 #define CROWDSTEP_STATE_H
@@ -279,6 +316,34 @@ size_t cs_close_pairs(cs_engine*, double distance, const cs_selection* sel_a, co
  * collectives depends neither on the crowd nor on the answer.  A tile that fails makes every rank return SIZE_MAX. */
 size_t cs_mesh_close_pairs(cs_mesh*, double distance, const cs_selection* sel_a, const cs_selection* sel_b,
                            cs_id_pair* out_pairs, double* out_d2, size_t cap);
+
+typedef struct cs_cluster {      /* 64 bytes */
+  uint64_t label, size;                /* the smallest id among the members; their number       */
+  double min_x, min_y, max_x, max_y;   /* of the members' reported positions: exact              */
+  double sum_x, sum_y;                 /* f64 sums of them: centroid = sum / size                */
+} cs_cluster;
+/* The clusters of the members under the links of `distance`: connected components, labelled by their smallest id.
+ * members == NULL: everyone.  Only clusters of at least min_size members are reported.  out_ids / out_labels (agent_cap
+ * entries): the members of reported clusters, ascending by id, and the label of each; out_clusters (cluster_cap entries):
+ * the reported clusters, ascending by label; *n_agents / *n_clusters: the full counts.  Every output may be NULL
+ * (out_labels only with out_ids).  0 = Ok. */
+int cs_agent_clusters(cs_engine*, double distance, const cs_selection* members, uint64_t min_size,
+                      uint64_t* out_ids, uint64_t* out_labels, size_t agent_cap, size_t* n_agents,
+                      cs_cluster* out_clusters, size_t cluster_cap, size_t* n_clusters);
+/* The same on a mesh.  Collective: every rank passes the same arguments and gets the whole answer, byte for byte the
+ * single engine's except sum_x / sum_y, which are under their bound.  On a mesh of more than one tile `distance` is at
+ * most halo_cells * cell_size.  No halo exchange is made for it and the step's own exchange state is left as it is: every
+ * tile clusters the agents it owns and exports a band record (id, position, local label, tile) of each member within
+ * reach of an edge behind which another tile lies; one gather brings these records to every rank, each rank finds on the
+ * device the links between its tiles' band agents and the records of the tiles with a higher index and reduces them to
+ * distinct (local label, foreign label) pairs, a second gather moves those, every rank runs the same small union-find
+ * over labels, applies the label map on the device and merges the per-cluster rows: sizes add, boxes merge, sums add in
+ * tile-index order.  A third gather carries the answer.  The number of collectives depends neither on the crowd nor on
+ * the answer; what travels before the answer grows with the agents near cuts, not with the crowd.  A tile that fails
+ * makes every rank return Err. */
+int cs_mesh_agent_clusters(cs_mesh*, double distance, const cs_selection* members, uint64_t min_size,
+                           uint64_t* out_ids, uint64_t* out_labels, size_t agent_cap, size_t* n_agents,
+                           cs_cluster* out_clusters, size_t cluster_cap, size_t* n_clusters);
 
 #ifdef __cplusplus
 }

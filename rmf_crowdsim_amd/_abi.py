@@ -279,8 +279,16 @@ class IdPair(C.Structure):
     _fields_ = [("a", C.c_uint64), ("b", C.c_uint64)]
 
 
+class Cluster(C.Structure):
+    """cs_cluster: one cluster of cs_agent_clusters (include/crowdstep_state.h)"""
+    _fields_ = [("label", C.c_uint64), ("size", C.c_uint64), ("min_x", C.c_double), ("min_y", C.c_double),
+                ("max_x", C.c_double), ("max_y", C.c_double), ("sum_x", C.c_double), ("sum_y", C.c_double)]
+
+
 _PAIRS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.POINTER(IdPair), C.POINTER(C.c_double),
                C.c_size_t]
+_CLUSTERS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                  C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(Cluster), C.c_size_t, C.POINTER(C.c_size_t)]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -309,6 +317,8 @@ STATE_SYMBOLS = {
     "cs_mesh_field_gather_bytes": (C.c_uint64, [C.c_void_p]),
     "cs_close_pairs": (C.c_size_t, list(_PAIRS_ARGS)),
     "cs_mesh_close_pairs": (C.c_size_t, list(_PAIRS_ARGS)),
+    "cs_agent_clusters": (C.c_int, list(_CLUSTERS_ARGS)),
+    "cs_mesh_agent_clusters": (C.c_int, list(_CLUSTERS_ARGS)),
 }
 
 

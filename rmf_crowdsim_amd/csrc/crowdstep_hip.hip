@@ -22,6 +22,7 @@
 //   cs_select.hip.inc         selecting, counting and removing agents by region, owner and state (the same header)
 //   cs_field.hip.inc          rasterising the crowd into a grid (the same header)
 //   cs_close_pairs.hip.inc    the pairs of agents within a distance of one another (the same header)
+//   cs_clusters.hip.inc       the clusters of agents under that distance: union-find on the device (the same header)
 //   this file                 includes + the extern "C" boundary
 //
 // Device state is f32 and CELL-RELATIVE: an agent is (stored cell, offset from
@@ -1257,3 +1258,4 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_select.hip.inc"
 #include "cs_field.hip.inc"
 #include "cs_close_pairs.hip.inc"
+#include "cs_clusters.hip.inc"

@@ -646,6 +646,58 @@ def close_pairs_of(fn, handle, handle_of, err, distance, a, b, limit, distances)
     return (pairs, d2) if distances else pairs
 
 
+CLUSTER_DTYPE = np.dtype([("label", np.uint64), ("size", np.uint64), ("min_x", np.float64), ("min_y", np.float64),
+                          ("max_x", np.float64), ("max_y", np.float64), ("sum_x", np.float64), ("sum_y", np.float64)])
+assert CLUSTER_DTYPE.itemsize == C.sizeof(_abi.Cluster)
+
+
+def agent_clusters_call(fn, handle, distance, sel, min_size, agent_cap, cluster_cap):
+    """cs_agent_clusters / cs_mesh_agent_clusters with room for `agent_cap` members and `cluster_cap` clusters -> (rc,
+    n_agents, n_clusters, uint64 ids, uint64 labels, CLUSTER_DTYPE table).  sel: an _abi.Selection or None (everyone); a
+    cap of 0: that list is not asked for."""
+    agent_cap, cluster_cap = max(int(agent_cap), 0), max(int(cluster_cap), 0)
+    ids = np.zeros(max(agent_cap, 1), dtype=np.uint64)
+    labels = np.zeros(max(agent_cap, 1), dtype=np.uint64)
+    table = np.zeros(max(cluster_cap, 1), dtype=CLUSTER_DTYPE)
+    n_agents, n_clusters = C.c_size_t(0), C.c_size_t(0)
+    u64 = C.POINTER(C.c_uint64)
+    rc = fn(handle, float(distance), C.byref(sel) if sel is not None else None, int(min_size),
+            ids.ctypes.data_as(u64) if agent_cap else None, labels.ctypes.data_as(u64) if agent_cap else None, agent_cap,
+            C.byref(n_agents), table.ctypes.data_as(C.POINTER(_abi.Cluster)) if cluster_cap else None, cluster_cap,
+            C.byref(n_clusters))
+    if rc != 0:
+        return rc, 0, 0, ids[:0].copy(), labels[:0].copy(), table[:0].copy()
+    na, nc = min(n_agents.value, agent_cap), min(n_clusters.value, cluster_cap)
+    return rc, n_agents.value, n_clusters.value, ids[:na].copy(), labels[:na].copy(), table[:nc].copy()
+
+
+def agent_clusters_of(fn, handle, handle_of, err, distance, members, min_size, limit):
+    """agent_clusters of Simulation and NativeTileMesh: limit=None lists everything (one counting call first)"""
+    if int(min_size) < 0:
+        raise CrowdSimError("agent_clusters: min_size is negative")
+    sel = None if members is None else selection_struct(members, handle_of)
+    if limit is None:
+        rc, agent_cap, cluster_cap, _, _, _ = agent_clusters_call(fn, handle, distance, sel, min_size, 0, 0)
+        if rc != 0:
+            raise err()
+    else:
+        agent_cap = cluster_cap = max(int(limit), 0)
+    rc, _, _, ids, labels, table = agent_clusters_call(fn, handle, distance, sel, min_size, agent_cap, cluster_cap)
+    if rc != 0:
+        raise err()
+    return ids, labels, table
+
+
+def count_clusters_of(fn, handle, handle_of, err, distance, members, min_size):
+    if int(min_size) < 0:
+        raise CrowdSimError("agent_clusters: min_size is negative")
+    sel = None if members is None else selection_struct(members, handle_of)
+    rc, n_agents, n_clusters, _, _, _ = agent_clusters_call(fn, handle, distance, sel, min_size, 0, 0)
+    if rc != 0:
+        raise err()
+    return int(n_clusters), int(n_agents)
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -1003,6 +1055,25 @@ class Simulation:
         if n is None:
             raise self._err()
         return int(n)
+
+    def agent_clusters(self, distance, members=None, *, min_size=1, limit=None):
+        """Which agents hang together, on the device (cs_agent_clusters): jams, groups, contact chains.  The clusters are
+        the connected components of the members under the links of close_pairs(distance, members, members); `members` is
+        what select_agents accepts (None: everyone), and an agent that is no member bridges nobody.  Returns (ids
+        uint64[n], labels uint64[n], table): the members of the reported clusters ascending by id, the label of each (the
+        smallest id of its cluster), and a structured array (label, size, min_x, min_y, max_x, max_y, sum_x, sum_y) of the
+        clusters ascending by label; the centroid is sum / size.  Only clusters of at least `min_size` members are
+        reported; `limit`: at most that many entries of each list (the first ones).  Changes nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_agent_clusters", "agent_clusters")
+        return agent_clusters_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, members,
+                                 min_size, limit)
+
+    def count_clusters(self, distance, members=None, *, min_size=1):
+        """(number of clusters, number of their members) of agent_clusters(distance, members, min_size=min_size), from a
+        call that lists nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_agent_clusters", "agent_clusters")
+        return count_clusters_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, members,
+                                 min_size)
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

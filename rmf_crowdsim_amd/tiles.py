@@ -756,6 +756,23 @@ class NativeTileMesh:
             raise self._err()
         return int(n)
 
+    def agent_clusters(self, distance, members=None, *, min_size=1, limit=None):
+        """Simulation.agent_clusters on the mesh (cs_mesh_agent_clusters): the single engine's answer, byte for byte except
+        the sums, which are under their bound.  On a mesh of more than one tile `distance` is at most halo_cells *
+        cell_size.  Every tile clusters its own agents; the members near a cut travel as band records with their local
+        label, the labels linked across cuts are merged by one small union-find; no halo exchange is made.  Collective in
+        the distributed form: every rank passes the same arguments and gets the whole answer."""
+        from .simulation import agent_clusters_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_agent_clusters", "agent_clusters")
+        return agent_clusters_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, members, min_size,
+                                 limit)
+
+    def count_clusters(self, distance, members=None, *, min_size=1):
+        """Simulation.count_clusters on the mesh (collective in the distributed form)."""
+        from .simulation import count_clusters_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_agent_clusters", "agent_clusters")
+        return count_clusters_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, members, min_size)
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
