@@ -516,6 +516,29 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     c.agents = na;
     return c;
   }
+  // What surrounds each agent (cs_agent_neighbours, include/crowdstep_state.h "Neighbours of each agent between steps"):
+  // for every subject (`subjects`, null: everyone) the number of others (`others`, null: everyone; itself never) closer
+  // than `distance` and the nearest of them (ties: the smallest id), ascending by id; only subjects with
+  // count >= min_count are reported (0: all).  `limit`: at most that many rows (the first ones).
+  std::vector<cs_neighbour_stat> agent_neighbours(double distance, const cs_selection* subjects = nullptr,
+                                                  const cs_selection* others = nullptr, uint64_t min_count = 0,
+                                                  std::size_t limit = SIZE_MAX) {
+    std::vector<cs_neighbour_stat> out;
+    const std::size_t cap = (std::size_t)std::min<uint64_t>(
+        count_agents_with_neighbours(distance, subjects, others, min_count), limit);
+    if (!cap) return out;
+    out.resize(cap);
+    const std::size_t n = cs_agent_neighbours(engine_, distance, subjects, others, min_count, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  uint64_t count_agents_with_neighbours(double distance, const cs_selection* subjects = nullptr,
+                                        const cs_selection* others = nullptr, uint64_t min_count = 1) {
+    const std::size_t n = cs_agent_neighbours(engine_, distance, subjects, others, min_count, nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return n;
+  }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
     std::vector<AgentId> ids(cs_agent_count(engine_));
@@ -825,6 +848,29 @@ class TiledSimulation {
     c.clusters = nc;
     c.agents = na;
     return c;
+  }
+  // What surrounds each agent (cs_mesh_agent_neighbours, include/crowdstep_state.h "Neighbours of each agent between steps"):
+  // for every subject (`subjects`, null: everyone) the number of others (`others`, null: everyone; itself never) closer
+  // than `distance` and the nearest of them (ties: the smallest id), ascending by id; only subjects with
+  // count >= min_count are reported (0: all).  `limit`: at most that many rows (the first ones).
+  std::vector<cs_neighbour_stat> agent_neighbours(double distance, const cs_selection* subjects = nullptr,
+                                                  const cs_selection* others = nullptr, uint64_t min_count = 0,
+                                                  std::size_t limit = SIZE_MAX) {
+    std::vector<cs_neighbour_stat> out;
+    const std::size_t cap = (std::size_t)std::min<uint64_t>(
+        count_agents_with_neighbours(distance, subjects, others, min_count), limit);
+    if (!cap) return out;
+    out.resize(cap);
+    const std::size_t n = cs_mesh_agent_neighbours(mesh_, distance, subjects, others, min_count, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  uint64_t count_agents_with_neighbours(double distance, const cs_selection* subjects = nullptr,
+                                        const cs_selection* others = nullptr, uint64_t min_count = 1) {
+    const std::size_t n = cs_mesh_agent_neighbours(mesh_, distance, subjects, others, min_count, nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return n;
   }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {

@@ -184,6 +184,40 @@
  *     alone; nothing is renumbered.  The call may sort the arrays by cell, as the spatial queries do: the next step runs
  *     to the same bytes as on an engine that never made the call.  The device scratch of a call is kept while it is at
  *     most 16 MiB (the scratch of cs_close_pairs, part of cs_device_bytes); a larger one is freed before the call returns.
+ *
+ * Neighbours of each agent between steps ("Neighbours of each agent between steps"): the question
+ * about EACH agent and its surroundings: how many people stand within 1 m of this person (local density), whose personal
+ * space is violated right now, which pedestrian is closest to each robot and how far, how many agents have nobody within
+ * 3 m.  cs_agent_neighbours answers on the device from the cell-sorted arrays; what comes to the host is at most one
+ * 32-byte row per agent, never a pair.
+ *   - An agent is the record cs_read_agents returns for it at that moment: x, y the reported f64 position.
+ *   - It TAKES PART by the rule of cs_close_pairs: a finite reported position inside the grid's own rectangle; on a tile
+ *     engine and on a mesh the rectangle is the GLOBAL grid's.  A SUBJECT is a participant that satisfies `subjects`, an
+ *     OTHER a participant that satisfies `others`, both judged exactly as for cs_select_agents, NULL: everyone.  Agents
+ *     the index never took, clamped agents, aliased agents and NaN agents are neither subject nor other.  On a tile engine
+ *     whose arrays hold ghosts only owned agents are subjects or others.
+ *   - An other q != p is a NEIGHBOUR of subject p iff dx * dx + dy * dy < distance * distance with dx = x_p - x_q,
+ *     dy = y_p - y_q: f64, every difference, product and sum rounded once (no contraction, no f32 pre-reject), the
+ *     comparison strict.  This is the expression of cs_close_pairs: with subjects == others == NULL the counts of all rows
+ *     sum to exactly 2 * cs_close_pairs(distance, NULL, NULL).  A subject that is also an other does not count itself.
+ *     Two agents on one point are neighbours for any distance > 0, with nearest_d2 == +0.0.  distance = 0: every subject
+ *     has count 0.  distance = +inf: every other but itself is a neighbour (on a single engine; a mesh of more than one
+ *     tile refuses +inf, as for the pairs).
+ *   - `nearest` is the neighbour with the smallest nearest_d2, among equal values the one with the smallest id (external
+ *     ids under CS_CFG_WIDE_IDS; ascending device id is ascending external id).  So the row depends neither on the order
+ *     of the slots, nor on tiles, nor on the order of the walk.
+ *   - min_count: a subject is REPORTED iff count >= min_count; 0 reports every subject, the isolated ones included.
+ *   - The answer: the call returns the number of reported subjects and writes the first min(that, cap) rows, ascending by
+ *     id.  Nothing is written beyond them.
+ *   - out == NULL or cap == 0: the number only, from a pass that materialises no row (one 64-bit tally per workgroup):
+ *     "how many people have somebody within 0.4 m" in one launch.
+ *   - Refused with SIZE_MAX, nothing written, the engine or mesh usable: a NaN or negative distance, a selection
+ *     cs_select_agents refuses, and on a mesh of more than one tile a distance above halo_cells * cell_size.  There is no
+ *     limit in the style of CS_PAIRS_MAX: the answer never exceeds one row per agent.
+ *   - Queued steps complete first and a failure of one of them is the call's; no events; the last step report is left
+ *     alone; nothing is renumbered.  The call may sort the arrays by cell, as the spatial queries do: the next step runs
+ *     to the same bytes as on an engine that never made the call.  The device scratch of a call is kept while it is at
+ *     most 16 MiB (the scratch of cs_close_pairs, part of cs_device_bytes); a larger one is freed before the call returns.
  */
 #ifndef CROWDSTEP_STATE_H
 #define CROWDSTEP_STATE_H
@@ -344,6 +378,32 @@ int cs_agent_clusters(cs_engine*, double distance, const cs_selection* members, 
 int cs_mesh_agent_clusters(cs_mesh*, double distance, const cs_selection* members, uint64_t min_size,
                            uint64_t* out_ids, uint64_t* out_labels, size_t agent_cap, size_t* n_agents,
                            cs_cluster* out_clusters, size_t cluster_cap, size_t* n_clusters);
+
+#define CS_NO_NEIGHBOUR UINT64_MAX
+typedef struct cs_neighbour_stat {   /* 32 bytes */
+  uint64_t id;          /* the subject                                                    */
+  uint64_t count;       /* others within `distance` of it, itself not among them: exact   */
+  uint64_t nearest;     /* the closest of them; CS_NO_NEIGHBOUR when count == 0            */
+  double   nearest_d2;  /* its squared distance, bit for bit; +inf when count == 0         */
+} cs_neighbour_stat;
+/* For each subject, the number of others closer than `distance` and the nearest of them.  Returns the number of subjects
+ * with count >= min_count and writes the first min(that, cap) rows, ascending by id; out == NULL or cap == 0: the number
+ * only.  subjects / others: NULL: everyone.  SIZE_MAX on error. */
+size_t cs_agent_neighbours(cs_engine*, double distance, const cs_selection* subjects, const cs_selection* others,
+                           uint64_t min_count, cs_neighbour_stat* out, size_t cap);
+/* The same on a mesh.  Collective: every rank passes the same arguments and gets the whole answer, byte for byte the
+ * single engine's: counts add exactly and `nearest` is a lexicographic minimum of (d2, id).  On a mesh of more than one
+ * tile `distance` is at most halo_cells * cell_size (so +inf is refused there).  No halo exchange is made and the step's
+ * own exchange state is left as it is: every tile computes the rows of the subjects it owns against the others it owns
+ * and keeps them on its device; it exports a band record (id, position, bit 0 subject / bit 1 other, tile) of each
+ * participant within reach of an edge behind which another tile lies; one gather brings these records to every rank;
+ * each rank tests, on the device, its tiles' band subjects against the band others of every other tile and merges count
+ * and (d2, id) into the subject's row; min_count is applied after that; a last gather carries the reported rows (the
+ * count-only form: the counts) and every rank merges the id-sorted runs.  The number of collectives depends neither on
+ * the crowd nor on the answer; what travels before the answer grows with the agents near cuts.  A tile that fails makes
+ * every rank return SIZE_MAX. */
+size_t cs_mesh_agent_neighbours(cs_mesh*, double distance, const cs_selection* subjects, const cs_selection* others,
+                                uint64_t min_count, cs_neighbour_stat* out, size_t cap);
 
 #ifdef __cplusplus
 }

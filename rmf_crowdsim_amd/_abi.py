@@ -257,6 +257,7 @@ CS_SEL_RECT, CS_SEL_CIRCLE, CS_SEL_SOURCE_SINK, CS_SEL_HLP, CS_SEL_LP, CS_SEL_WA
 CS_SELECT_MAX = 1024
 CS_FIELD_MAX_CELLS = 4194304
 CS_PAIRS_MAX = 1 << 26
+CS_NO_NEIGHBOUR = 0xFFFFFFFFFFFFFFFF
 
 
 class Selection(C.Structure):
@@ -285,10 +286,17 @@ class Cluster(C.Structure):
                 ("max_x", C.c_double), ("max_y", C.c_double), ("sum_x", C.c_double), ("sum_y", C.c_double)]
 
 
+class NeighbourStat(C.Structure):
+    """cs_neighbour_stat: one subject of cs_agent_neighbours (include/crowdstep_state.h)"""
+    _fields_ = [("id", C.c_uint64), ("count", C.c_uint64), ("nearest", C.c_uint64), ("nearest_d2", C.c_double)]
+
+
 _PAIRS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.POINTER(IdPair), C.POINTER(C.c_double),
                C.c_size_t]
 _CLUSTERS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                   C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(Cluster), C.c_size_t, C.POINTER(C.c_size_t)]
+_NEIGHBOURS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.c_uint64,
+                    C.POINTER(NeighbourStat), C.c_size_t]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -319,6 +327,8 @@ STATE_SYMBOLS = {
     "cs_mesh_close_pairs": (C.c_size_t, list(_PAIRS_ARGS)),
     "cs_agent_clusters": (C.c_int, list(_CLUSTERS_ARGS)),
     "cs_mesh_agent_clusters": (C.c_int, list(_CLUSTERS_ARGS)),
+    "cs_agent_neighbours": (C.c_size_t, list(_NEIGHBOURS_ARGS)),
+    "cs_mesh_agent_neighbours": (C.c_size_t, list(_NEIGHBOURS_ARGS)),
 }
 
 

@@ -23,6 +23,7 @@
 //   cs_field.hip.inc          rasterising the crowd into a grid (the same header)
 //   cs_close_pairs.hip.inc    the pairs of agents within a distance of one another (the same header)
 //   cs_clusters.hip.inc       the clusters of agents under that distance: union-find on the device (the same header)
+//   cs_neighbours.hip.inc     per agent: how many others within a distance, and the nearest of them (the same header)
 //   this file                 includes + the extern "C" boundary
 //
 // Device state is f32 and CELL-RELATIVE: an agent is (stored cell, offset from
@@ -1259,3 +1260,4 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_field.hip.inc"
 #include "cs_close_pairs.hip.inc"
 #include "cs_clusters.hip.inc"
+#include "cs_neighbours.hip.inc"

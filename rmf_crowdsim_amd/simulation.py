@@ -698,6 +698,41 @@ def count_clusters_of(fn, handle, handle_of, err, distance, members, min_size):
     return int(n_clusters), int(n_agents)
 
 
+NEIGHBOUR_DTYPE = np.dtype([("id", np.uint64), ("count", np.uint64), ("nearest", np.uint64), ("nearest_d2", np.float64)])
+assert NEIGHBOUR_DTYPE.itemsize == C.sizeof(_abi.NeighbourStat) == 32
+
+
+def agent_neighbours_call(fn, handle, distance, sel_subjects, sel_others, min_count, cap):
+    """cs_agent_neighbours / cs_mesh_agent_neighbours with room for `cap` rows -> (the number of reported subjects, or
+    None on error; the first min(number, cap) rows as a NEIGHBOUR_DTYPE array).  sel_subjects / sel_others: an
+    _abi.Selection or None (everyone); cap == 0: the number only."""
+    cap = max(int(cap), 0)
+    rows = np.zeros(max(cap, 1), dtype=NEIGHBOUR_DTYPE)
+    got = fn(handle, float(distance), C.byref(sel_subjects) if sel_subjects is not None else None,
+             C.byref(sel_others) if sel_others is not None else None, int(min_count),
+             rows.ctypes.data_as(C.POINTER(_abi.NeighbourStat)) if cap else None, cap)
+    if got == _SIZE_MAX:
+        return None, rows[:0].copy()
+    return got, rows[:min(got, cap)].copy()
+
+
+def agent_neighbours_of(fn, handle, handle_of, err, distance, subjects, others, min_count, limit):
+    """agent_neighbours and count_agents_with_neighbours of Simulation and NativeTileMesh.  limit=None lists every
+    reported subject (one counting call first), limit=0 only counts -> (number, rows)"""
+    if int(min_count) < 0:
+        raise CrowdSimError("agent_neighbours: min_count is negative")
+    sel_s = None if subjects is None else selection_struct(subjects, handle_of)
+    sel_o = None if others is None else selection_struct(others, handle_of)
+    if limit is None:
+        limit, _ = agent_neighbours_call(fn, handle, distance, sel_s, sel_o, min_count, 0)
+        if limit is None:
+            raise err()
+    n, rows = agent_neighbours_call(fn, handle, distance, sel_s, sel_o, min_count, limit)
+    if n is None:
+        raise err()
+    return int(n), rows
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -1074,6 +1109,25 @@ class Simulation:
         fn = state_fn(self._lib, self.backend, "cs_agent_clusters", "agent_clusters")
         return count_clusters_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, members,
                                  min_size)
+
+    def agent_neighbours(self, distance, subjects=None, others=None, *, min_count=0, limit=None):
+        """What surrounds each agent, on the device (cs_agent_neighbours): local density, violated personal space, the
+        pedestrian closest to each robot.  For every subject (an agent `subjects` selects, None: everyone) the number of
+        others (`others`, None: everyone; itself never) with dx*dx + dy*dy < distance*distance on the positions
+        read_agents() reports, in f64, and the nearest of them (ties: the smallest id).  Returns a structured array (id,
+        count, nearest, nearest_d2) ascending by id, of the subjects with count >= min_count (0: all, the isolated ones
+        with nearest == _abi.CS_NO_NEIGHBOUR and nearest_d2 == inf); `limit`: at most that many rows (the first ones).
+        Selections as for close_pairs.  Changes nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_agent_neighbours", "agent_neighbours")
+        return agent_neighbours_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, subjects,
+                                   others, min_count, limit)[1]
+
+    def count_agents_with_neighbours(self, distance, subjects=None, others=None, *, min_count=1):
+        """len(agent_neighbours(distance, subjects, others, min_count=min_count)) from a pass that lists no row: how many
+        people have somebody within 0.4 m, in one launch."""
+        fn = state_fn(self._lib, self.backend, "cs_agent_neighbours", "agent_neighbours")
+        return agent_neighbours_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, subjects,
+                                   others, min_count, 0)[0]
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

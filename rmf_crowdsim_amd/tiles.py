@@ -773,6 +773,23 @@ class NativeTileMesh:
         fn = state_fn(self._lib, "mesh", "cs_mesh_agent_clusters", "agent_clusters")
         return count_clusters_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, members, min_size)
 
+    def agent_neighbours(self, distance, subjects=None, others=None, *, min_count=0, limit=None):
+        """Simulation.agent_neighbours on the mesh (cs_mesh_agent_neighbours): the single engine's answer, byte for byte
+        (collective in the distributed form).  With more than one tile, distance <= halo_cells * cell_size.  Every tile
+        counts among its own agents; the participants near a cut travel as band records, each tile merges what its band
+        subjects find behind the cuts into their rows on its device, and min_count is applied after that."""
+        from .simulation import agent_neighbours_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_agent_neighbours", "agent_neighbours")
+        return agent_neighbours_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, subjects, others,
+                                   min_count, limit)[1]
+
+    def count_agents_with_neighbours(self, distance, subjects=None, others=None, *, min_count=1):
+        """Simulation.count_agents_with_neighbours on the mesh (collective in the distributed form)."""
+        from .simulation import agent_neighbours_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_agent_neighbours", "agent_neighbours")
+        return agent_neighbours_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, subjects, others,
+                                   min_count, 0)[0]
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
