@@ -21,6 +21,8 @@
 //   cs_set_targets.hip.inc    sending agents to goals by id, a batch at a time (the same header)
 //   cs_select.hip.inc         selecting, counting and removing agents by region, owner and state (the same header)
 //   cs_field.hip.inc          rasterising the crowd into a grid (the same header)
+//   cs_near.hip.inc           what the three distance queries below share: the walk over the cells in reach, the band of
+//                             a tile, the cross loop over the bands of other tiles, the block helpers, the sort of a list
 //   cs_close_pairs.hip.inc    the pairs of agents within a distance of one another (the same header)
 //   cs_clusters.hip.inc       the clusters of agents under that distance: union-find on the device (the same header)
 //   cs_neighbours.hip.inc     per agent: how many others within a distance, and the nearest of them (the same header)
@@ -40,6 +42,7 @@
 #include <array>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <thread>
@@ -1258,6 +1261,7 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_set_targets.hip.inc"
 #include "cs_select.hip.inc"
 #include "cs_field.hip.inc"
+#include "cs_near.hip.inc"
 #include "cs_close_pairs.hip.inc"
 #include "cs_clusters.hip.inc"
 #include "cs_neighbours.hip.inc"

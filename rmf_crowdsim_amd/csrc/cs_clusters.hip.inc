@@ -1,15 +1,15 @@
 // cs_clusters.hip.inc — which agents hang together, between steps: the connected components of the graph cs_close_pairs
 // defines (include/crowdstep_state.h, "Clusters of agents between steps").  Part of the single translation unit
-// crowdstep_hip.hip (included there, after cs_close_pairs.hip.inc; it uses pairs_self / pairs_in_grid / PairsArgs /
-// PairsScratch and the radix passes k_pairs_hist / k_ids_scan / k_pairs_scatter of that file, none of which it changes).
+// crowdstep_hip.hip (included there, after cs_close_pairs.hip.inc; it uses the walk, the band, the cross loop, the block
+// helpers, PairsScratch and the sort of cs_near.hip.inc and pairs_sort_download of cs_close_pairs.hip.inc, none of which
+// it changes).
 //
 //   K_init     k_clusters_init, one lane per slot of the CELL-SORTED arrays: parent[slot] = slot for a member (pairs_self
 //              with both roles set to `members`), CLU_NONE for everybody else.  Membership is judged once, here; every
 //              later kernel reads it from parent[].
-//   K_link     k_clusters_link, one lane per slot: the walk of pairs_walk restated (the same rectangle of cells, the same
-//              runs of cell_start, the same f64 expression, no pre-reject); for every linked candidate with a LARGER
-//              device id that is a member it unites the two trees: find both roots (path halving), hook the HIGHER root
-//              slot under the lower with one atomicCAS, and on a lost race find again.
+//   K_link     k_clusters_link, one lane per slot: near_walk; for every candidate in reach with a LARGER device id that
+//              is a member it unites the two trees: find both roots (path halving), hook the HIGHER root slot under the
+//              lower with one atomicCAS, and on a lost race find again.
 //   why it ends  parent[s] <= s always: K_init writes s, a hook writes a lower root into a root, halving writes an
 //              ancestor (lower still).  So every find walks strictly downwards, and every retry of a hook starts from a
 //              root that just got a lower parent: both loops end, whatever the other lanes do.  No lane waits for another:
@@ -26,11 +26,11 @@
 //   K_stats    k_clusters_stats: box and f64 sums per row, reduced per root in the wave like K_label, then one f64
 //              atomicMin / atomicMax / atomicAdd each per distinct root and wave; a cluster of one writes its row plainly.
 //   K_members  k_clusters_members: (id << 32 | label) of every member of a reported cluster, one atomic per workgroup.
-//   sort       the pairs' radix passes over the HIGH word of the keys; k_clusters_gather brings the rows into label
-//              order; only the first `cap` entries of either list are downloaded.
-//   mesh       k_clusters_band exports (position, id, local label, tile) of the members near a cut; k_clusters_cross_*
-//              find the links between a tile's band and the records of higher tiles and emit (local label, foreign
-//              label); k_clusters_relabel applies the merged label map to the member keys a tile holds.
+//   sort       pairs_radix over the HIGH word of the keys; k_clusters_gather brings the rows into label order; only the
+//              first `cap` entries of either list are downloaded.
+//   mesh       k_clusters_band exports (position, id, local label, tile) of the members in the band; k_clusters_cross_*
+//              find the links between a tile's band and the records of higher tiles (near_cross) and emit (local label,
+//              foreign label); k_clusters_relabel applies the merged label map to the member keys a tile holds.
 //
 // Scratch: 16 bytes per slot (parent, smallest id, size, row) plus, when listing, 64 + 16 bytes per reported cluster and
 // 16 per reported member, through PairsScratch: in cs_engine::pairs_scratch while at most PAIRS_SCRATCH_KEEP bytes, else
@@ -79,7 +79,7 @@ __device__ __forceinline__ void clu_unite(uint32_t* __restrict__ parent, uint32_
   }
 }
 
-// the f64 position of slot i, the expression of cs_engine::to_global (as sel_load and pairs_walk compute it)
+// the f64 position of slot i, the expression of cs_engine::to_global (as sel_load and near_walk compute it)
 __device__ __forceinline__ void clu_position(const GridDev& g, const AgentArrays& a, uint32_t i, const PairsArgs& P, double* x,
                                              double* y) {
   const uint32_t c = a.cell[i];
@@ -100,7 +100,17 @@ __global__ void __launch_bounds__(PAIRS_BLOCK)
   parent[i] = pairs_self(g, a, i, limit, groups, P, &s) ? i : CLU_NONE;
 }
 
-// K_link.  The walk is that of pairs_walk; a candidate's membership is its parent[] entry.
+// What a member does on its walk: one tree with every member in reach that has a larger id.
+struct ClustersLink {
+  uint32_t* parent;
+  uint32_t i, sid;
+  __device__ __forceinline__ bool take(const AgentArrays& a, uint32_t j) { return a.id[j] > sid; }
+  __device__ __forceinline__ void hit(const GridDev&, const AgentArrays&, const PairsArgs&, uint32_t j, double, double, double) {
+    if (clu_load(&parent[j]) != CLU_NONE) clu_unite(parent, i, j);  // (not a member: it links nobody)
+  }
+};
+
+// K_link.  A candidate's membership is its parent[] entry.
 __global__ void __launch_bounds__(PAIRS_BLOCK)
     k_clusters_link(GridDev g, AgentArrays a, uint32_t n_ub, const uint32_t* __restrict__ cell_start, PairsArgs P,
                     uint32_t* __restrict__ parent) {
@@ -109,34 +119,10 @@ __global__ void __launch_bounds__(PAIRS_BLOCK)
   if (i >= limit || clu_load(&parent[i]) == CLU_NONE) return;
   double sx, sy;
   clu_position(g, a, i, P, &sx, &sy);
-  const uint32_t sid = a.id[i];
+  ClustersLink v{parent, i, a.id[i]};
   const uint32_t c = a.cell[i];
   const uint32_t scx = c / g.nx, scy = c - scx * g.nx;
-  const long long lo_x = P.owned_only ? g.own_x0 : 0u, hi_x = P.owned_only ? g.own_x1 : g.ny;
-  const long long lo_y = P.owned_only ? g.own_y0 : 0u, hi_y = P.owned_only ? g.own_y1 : g.nx;
-  const long long R = P.reach;
-  const long long xl = max((long long)scx - R, lo_x), xh = min((long long)scx + R, hi_x - 1);
-  const long long yl = max((long long)scy - R, lo_y), yh = min((long long)scy + R, hi_y - 1);
-  if (yl > yh) return;
-  for (long long xr = xl; xr <= xh; ++xr) {
-    const uint32_t rowbase = (uint32_t)xr * g.nx;
-    const uint32_t b = cell_start[rowbase + (uint32_t)yl];
-    const uint32_t e = min(cell_start[rowbase + (uint32_t)yh + 1u], limit);
-    const double bx = (double)((uint64_t)g.org_x + (uint64_t)xr) * P.cell_size;
-    for (uint32_t j = b; j < e; ++j) {
-      if (a.id[j] <= sid) continue;
-      const uint32_t cyj = a.cell[j] - rowbase;
-      if (cyj > (uint32_t)yh) continue;
-      const float2 off = a.off[j];
-      const double xq = P.off_x + (bx + (double)off.x);
-      const double yq = P.off_y + ((double)((uint64_t)g.org_y + cyj) * P.cell_size + (double)off.y);
-      const double dx = sx - xq, dy = sy - yq;
-      const double d2 = dx * dx + dy * dy;
-      if (!(d2 < P.dist2)) continue;
-      if (clu_load(&parent[j]) == CLU_NONE) continue;  // (not a member: it links nobody)
-      clu_unite(parent, i, j);
-    }
-  }
+  near_walk(g, a, limit, cell_start, P, sx, sy, scx, scy, v);
 }
 
 // K_flatten.
@@ -319,8 +305,8 @@ __global__ void __launch_bounds__(PAIRS_BLOCK)
   if (k < take) out[k] = rows[(uint32_t)keys[k]];
 }
 
-// The band of a tile (the rule of k_pairs_band): the members near an owned edge behind which another tile lies, with the
-// label of their cluster on this tile.  One atomic per wave; records beyond cap are dropped (the host gives room for all).
+// The band of a tile (near_in_band): the members in it, with the label of their cluster on this tile.  Records beyond cap
+// are dropped (the host gives room for all).
 __global__ void __launch_bounds__(PAIRS_BLOCK)
     k_clusters_band(GridDev g, AgentArrays a, uint32_t n, PairsArgs P, const uint32_t* __restrict__ parent,
                     const uint32_t* __restrict__ min_id, uint32_t edges, uint32_t tile_index,
@@ -330,21 +316,11 @@ __global__ void __launch_bounds__(PAIRS_BLOCK)
   bool hit = root != CLU_NONE;
   if (hit) {
     const uint32_t c = a.cell[i];
-    const uint32_t cx = c / g.nx, cy = c - cx * g.nx;
-    const unsigned long long R = P.reach;
-    hit = ((edges & 1u) && (unsigned long long)cx < g.own_x0 + R) || ((edges & 2u) && cx + R >= g.own_x1) ||
-          ((edges & 4u) && (unsigned long long)cy < g.own_y0 + R) || ((edges & 8u) && cy + R >= g.own_y1);
+    const uint32_t cx = c / g.nx;
+    hit = near_in_band(g, P.reach, edges, cx, c - cx * g.nx);
   }
-  const unsigned long long m = __ballot(hit);
-  if (!m) return;
-  const uint32_t lane = __lane_id();
-  const int first = __ffsll((long long)m) - 1;
-  uint32_t base = 0;
-  if ((int)lane == first) base = atomicAdd(count, (uint32_t)__popcll(m));
-  base = __shfl(base, first, 64);
-  if (!hit) return;
-  const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  if (at >= cap) return;
+  const uint32_t at = near_wave_place(hit, count);
+  if (at >= cap) return;  // (NEAR_NO_PLACE is beyond every cap)
   ClusterBandRec r;
   clu_position(g, a, i, P, &r.x, &r.y);
   r.id = a.id[i];
@@ -354,34 +330,26 @@ __global__ void __launch_bounds__(PAIRS_BLOCK)
   out[at] = r;
 }
 
-// One lane per band record of the local tile against the n_f foreign records, staged in LDS (8 KiB) like
-// pairs_cross_walk.  A link gives the key (local label << 32 | foreign label).  Every lane of the workgroup runs the loop.
+// What a band record does with a foreign record in reach: a link, the key (local label << 32 | foreign label).
+template <bool EMIT>
+struct ClustersCrossVisit {
+  PairsSink<EMIT> out;
+  __device__ __forceinline__ void hit(const ClusterBandRec& me, const ClusterBandRec& q, double d2) {
+    out.put(me.label, q.label, d2);
+  }
+};
+
+// near_cross for clusters (s_f: 8 KiB).  Every lane of the workgroup calls this.
 template <bool EMIT>
 __device__ __forceinline__ uint32_t clusters_cross_walk(const ClusterBandRec& me, bool live,
                                                         const ClusterBandRec* __restrict__ foreign, uint32_t n_f,
                                                         double dist2, ClusterBandRec* s_f, unsigned long long at,
                                                         unsigned long long cap, unsigned long long* __restrict__ keys,
                                                         uint32_t* top) {
-  uint32_t n = 0;
-  for (uint32_t base = 0; base < n_f; base += PAIRS_BLOCK) {
-    __syncthreads();
-    if (base + threadIdx.x < n_f) s_f[threadIdx.x] = foreign[base + threadIdx.x];
-    __syncthreads();
-    const uint32_t m = min(PAIRS_BLOCK, n_f - base);
-    if (!live) continue;
-    for (uint32_t k = 0; k < m; ++k) {
-      const ClusterBandRec q = s_f[k];
-      const double dx = me.x - q.x, dy = me.y - q.y;
-      const double d2 = dx * dx + dy * dy;
-      if (!(d2 < dist2)) continue;
-      if (EMIT) {
-        if (at + n < cap) keys[at + n] = ((unsigned long long)me.label << 32) | q.label;
-        *top = max(*top, max(me.label, q.label));
-      }
-      ++n;
-    }
-  }
-  return n;
+  ClustersCrossVisit<EMIT> v{{at, cap, keys, nullptr, 0u, 0u}};
+  near_cross(me, live, foreign, n_f, dist2, s_f, v);
+  if (EMIT) *top = v.out.top;
+  return v.out.n;
 }
 
 __global__ void __launch_bounds__(PAIRS_BLOCK)
@@ -435,10 +403,7 @@ namespace {
 // a NaN or negative distance, a selection cs_select_agents refuses, labels without ids (3)
 int clusters_check(std::string* error, double distance, const cs_selection* members, const uint64_t* out_ids,
                    const uint64_t* out_labels) {
-  if (!(distance >= 0.0)) {
-    *error = "agent_clusters: the distance is NaN or negative";
-    return 3;
-  }
+  if (int rc = near_check_distance(error, distance, "agent_clusters")) return rc;
   if (members)
     if (int rc = sel_check(error, members, "agent_clusters")) return rc;
   if (out_labels && !out_ids) {
@@ -495,22 +460,11 @@ size_t clusters_hist_bytes(size_t count) {
   return sel_up(IDS_RADIX * std::max<size_t>((count + IDS_TILE - 1u) / IDS_TILE, 1u) * sizeof(uint32_t));
 }
 
-// The radix passes over the HIGH word of n keys, whose largest high word is below 2^bits.  *keys is the sorted array
-// afterwards.
+// The radix passes over the HIGH word of n keys, the largest of which is `top`.  *keys is the sorted array afterwards.
 int clusters_sort(cs_engine* e, unsigned long long** keys, unsigned long long** other, uint32_t* hist, uint32_t n,
                   uint32_t top) {
   if (n < 2u) return 0;
-  const uint32_t tiles = (n + IDS_TILE - 1u) / IDS_TILE;
-  const uint32_t bits = top ? 32u - (uint32_t)__builtin_clz(top) : 1u;
-  for (uint32_t shift = 32u; shift < 32u + bits; shift += 4u) {
-    hipLaunchKernelGGL(k_pairs_hist, dim3(tiles), dim3(IDS_BLOCK), 0, e->stream, *keys, n, shift, hist, tiles);
-    hipLaunchKernelGGL(k_ids_scan, dim3(1), dim3(IDS_BLOCK), 0, e->stream, hist, IDS_RADIX * tiles);
-    hipLaunchKernelGGL(k_pairs_scatter, dim3(tiles), dim3(IDS_BLOCK), 0, e->stream, *keys, *other, (const double*)nullptr,
-                       (double*)nullptr, n, shift, hist, tiles);
-    std::swap(*keys, *other);
-  }
-  HIP_OK_E(e, hipGetLastError());
-  return 0;
+  return pairs_radix(e, keys, other, nullptr, nullptr, hist, n, 32u, pairs_bits(top));
 }
 
 // what one engine answers, in DEVICE ids: members as (id << 32 | label) ascending, rows ascending by label
@@ -536,23 +490,18 @@ struct ClustersHold {
   }
 };
 
-// mesh: the band of the tile, exported while the labels are on the device
-struct ClustersBand {
-  uint32_t edges = 0, tile_index = 0;
-  std::vector<ClusterBandRec> out;
-};
-
 // The clusters among the agents one engine holds (after sel_begin).  The counts always; with want_ids / want_rows > 0 the
-// first min(count, want) members / rows.  hold: the member keys stay on the device instead (all of them).
+// first min(count, want) members / rows.  hold: the member keys stay on the device instead (all of them).  band (mesh):
+// the band of the tile with these edges, exported while the labels are on the device.
 int clusters_run(cs_engine* e, const PairsArgs& P, uint64_t min_size, size_t want_ids, size_t want_rows, ClustersOut* out,
-                 ClustersHold* hold, ClustersBand* band) {
+                 ClustersHold* hold, uint32_t edges, uint32_t tile_index, std::vector<ClusterBandRec>* band) {
   *out = ClustersOut();
-  if (band) band->out.clear();
+  if (band) band->clear();
   if (int rc = e->refresh_counts()) return rc;
   if (int rc = e->ensure_index()) return rc;
   const uint32_t n = e->n_slots;
   if (!n) return 0;
-  const bool want_band = band && band->edges && P.dist2 > 0.0;
+  const bool want_band = band && edges && P.dist2 > 0.0;
   const size_t b_col = sel_up((size_t)n * sizeof(uint32_t));
   const size_t b_band = want_band ? 256u + sel_up((size_t)n * sizeof(ClusterBandRec)) : 0u;
   const size_t first = 256u + 4u * b_col + b_band;
@@ -586,8 +535,8 @@ int clusters_run(cs_engine* e, const PairsArgs& P, uint64_t min_size, size_t wan
   hipLaunchKernelGGL(k_clusters_tally, grid, block, 0, e->stream, parent, n, min_id, size, (unsigned long long)min_size, hdr);
   if (want_band) {
     HIP_OK_E(e, hipMemsetAsync(band_count, 0, sizeof(uint32_t), e->stream));
-    hipLaunchKernelGGL(k_clusters_band, grid, block, 0, e->stream, e->gdev, e->buf[e->cur], n, P, parent, min_id, band->edges,
-                       band->tile_index, band_rec, n, band_count);
+    hipLaunchKernelGGL(k_clusters_band, grid, block, 0, e->stream, e->gdev, e->buf[e->cur], n, P, parent, min_id, edges, tile_index,
+                       band_rec, n, band_count);
   }
   HIP_OK_E(e, hipGetLastError());
   unsigned long long back[3] = {0, 0, 0};
@@ -602,8 +551,8 @@ int clusters_run(cs_engine* e, const PairsArgs& P, uint64_t min_size, size_t wan
   out->n_clusters = back[0];
   out->n_agents = back[1];
   if (n_band) {
-    band->out.resize(n_band);
-    HIP_OK_E(e, hipMemcpyAsync(band->out.data(), band_rec, (size_t)n_band * sizeof(ClusterBandRec), hipMemcpyDeviceToHost,
+    band->resize(n_band);
+    HIP_OK_E(e, hipMemcpyAsync(band->data(), band_rec, (size_t)n_band * sizeof(ClusterBandRec), hipMemcpyDeviceToHost,
                                e->stream));
     HIP_OK_E(e, hipStreamSynchronize(e->stream));
   }
@@ -724,8 +673,7 @@ int clusters_cross(cs_engine* e, const std::vector<ClusterBandRec>& local, const
   hipLaunchKernelGGL(k_clusters_cross_count, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, d_l, n_l, d_f, n_f, dist2, hdr);
   HIP_OK_E(e, hipGetLastError());
   unsigned long long found = 0;
-  HIP_OK_E(e, hipMemcpyAsync(&found, hdr, sizeof found, hipMemcpyDeviceToHost, e->stream));
-  HIP_OK_E(e, hipStreamSynchronize(e->stream));
+  if (int rc = pairs_read_count(e, hdr, &found)) return rc;
   if (!found) return 0;
   if (found > CS_PAIRS_MAX) {
     e->error = "agent_clusters: too many links across the cuts of the mesh";
@@ -740,9 +688,8 @@ int clusters_cross(cs_engine* e, const std::vector<ClusterBandRec>& local, const
   hipLaunchKernelGGL(k_clusters_cross_emit, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, d_l, n_l, d_f, n_f, dist2, hdr, S.keys,
                      (unsigned long long)found);
   HIP_OK_E(e, hipGetLastError());
-  unsigned long long back[3] = {0, 0, 0};
-  HIP_OK_E(e, hipMemcpyAsync(back, hdr, sizeof back, hipMemcpyDeviceToHost, e->stream));
-  HIP_OK_E(e, hipStreamSynchronize(e->stream));
+  unsigned long long back[3];
+  if (int rc = pairs_read_header(e, hdr, back)) return rc;
   if (back[1] != found) {
     e->error = "agent_clusters: the listing found another number of links than the count";
     return 90;
@@ -776,7 +723,8 @@ int cs_agent_clusters(cs_engine* e, double distance, const cs_selection* members
   if (int rc = sel_begin(e)) return rc;
   const PairsArgs P = pairs_args(e, distance, members, members);
   ClustersOut r;
-  if (int rc = clusters_run(e, P, min_size, out_ids ? agent_cap : 0u, out_clusters ? cluster_cap : 0u, &r, nullptr, nullptr))
+  if (int rc = clusters_run(e, P, min_size, out_ids ? agent_cap : 0u, out_clusters ? cluster_cap : 0u, &r, nullptr, 0u, 0u,
+                            nullptr))
     return rc;
   clusters_copy_out(e, r, out_ids, out_labels, agent_cap, n_agents, out_clusters, cluster_cap, n_clusters);
   return 0;
@@ -790,10 +738,7 @@ int cs_mesh_agent_clusters(cs_mesh* m, double distance, const cs_selection* memb
   if (!m) return 3;
   if (m->dead()) return m->poison_rc;
   if (int rc = clusters_check(&m->error, distance, members, out_ids, out_labels)) return rc;
-  if (m->n_tiles() > 1u && distance > (double)m->halo * m->grid.cell_size) {
-    m->error = "agent_clusters: on a mesh of more than one tile the distance is at most halo_cells * cell_size";
-    return 3;
-  }
+  if (int rc = near_check_mesh_distance(m, distance, "agent_clusters")) return rc;
   if (int rc = cs_mesh_synchronize(m)) return rc;
   hipSetDevice(m->device);
   const bool want_ids = out_ids != nullptr && agent_cap > 0u;
@@ -804,47 +749,19 @@ int cs_mesh_agent_clusters(cs_mesh* m, double distance, const cs_selection* memb
   // 1. every tile: all clusters among the agents it owns (rows to the host, member keys kept on the device), its band
   std::vector<ClustersOut> parts(n_local);
   std::vector<ClustersHold> holds(n_local);
-  std::vector<ClustersBand> bands(n_local);
+  std::vector<std::vector<ClusterBandRec>> bands(n_local);
   for (size_t k = 0; k < n_local; ++k) {
     cs_engine* e = m->tiles[k];
     if (!err) err = sel_begin(e);
     const PairsArgs P = pairs_args(e, distance, members, members);
-    bands[k].tile_index = m->index_of[k];
-    if (m->n_tiles() > 1u)
-      for (int d = 0; d < 4; ++d)
-        if (m->neighbour(m->index_of[k], d) >= 0) bands[k].edges |= 1u << d;
-    if (!err) err = clusters_run(e, P, 1u, 0u, SIZE_MAX, &parts[k], want_ids ? &holds[k] : nullptr, &bands[k]);
+    if (!err)
+      err = clusters_run(e, P, 1u, 0u, SIZE_MAX, &parts[k], want_ids ? &holds[k] : nullptr, mesh_tile_edges(m, k), m->index_of[k],
+                         &bands[k]);
     if (err && why.empty()) why = cs_last_error(e);
   }
-  // 2. the band records of every tile on every rank: [failed?], then the records as four words each
+  // 2. the band records of every tile on every rank
   std::vector<ClusterBandRec> every;
-  if (m->distributed) {
-    std::vector<uint64_t> mine(1, err ? 1u : 0u);
-    if (!err)
-      for (const auto& b : bands) {
-        const size_t at = mine.size();
-        mine.resize(at + 4u * b.out.size());
-        if (!b.out.empty()) std::memcpy(&mine[at], b.out.data(), b.out.size() * sizeof(ClusterBandRec));
-      }
-    std::vector<std::vector<unsigned char>> got;
-    if (int rc = mesh_host_gatherv(m, mine.data(), mine.size() * sizeof(uint64_t), got)) return m->poison(rc, m->error);
-    for (const auto& part : got) {
-      uint64_t failed = 1u;
-      if (part.size() >= sizeof failed) std::memcpy(&failed, part.data(), sizeof failed);
-      if (failed || (part.size() - sizeof(uint64_t)) % sizeof(ClusterBandRec)) {
-        if (!err) {
-          err = 90;
-          why = "a tile of another rank failed while clustering agents";
-        }
-        continue;
-      }
-      const size_t k = (part.size() - sizeof(uint64_t)) / sizeof(ClusterBandRec), at = every.size();
-      every.resize(at + k);
-      if (k) std::memcpy(&every[at], part.data() + sizeof(uint64_t), k * sizeof(ClusterBandRec));
-    }
-  } else {
-    for (const auto& b : bands) every.insert(every.end(), b.out.begin(), b.out.end());
-  }
+  if (int rc = mesh_gather_bands(m, bands, "a tile of another rank failed while clustering agents", &err, &why, &every)) return rc;
   // 3. every local tile's band against the records of the tiles with a higher index: the distinct label links
   std::vector<uint64_t> links;
   for (size_t k = 0; k < n_local && !err; ++k) {
@@ -852,7 +769,7 @@ int cs_mesh_agent_clusters(cs_mesh* m, double distance, const cs_selection* memb
     for (const ClusterBandRec& r : every)
       if (r.tile > m->index_of[k]) foreign.push_back(r);
     std::vector<uint64_t> part;
-    err = clusters_cross(m->tiles[k], bands[k].out, foreign, dist2, &part);
+    err = clusters_cross(m->tiles[k], bands[k], foreign, dist2, &part);
     if (err && why.empty()) why = cs_last_error(m->tiles[k]);
     links.insert(links.end(), part.begin(), part.end());
   }

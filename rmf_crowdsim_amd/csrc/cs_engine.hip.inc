@@ -2763,7 +2763,7 @@ struct cs_engine {
     b += write_scratch_bytes;  // the batches of the by-id calls (write, read, remove) and the selections' lists
     b += sel_groups_cap * sizeof(SelGroupDev);
     b += field_scratch_bytes;  // the raster of the last cs_agent_field (cs_field.hip.inc)
-    b += pairs_scratch_bytes;  // the kept part of the pair lists of cs_close_pairs, at most 16 MiB (cs_close_pairs.hip.inc)
+    b += pairs_scratch_bytes;  // the kept part of the lists of the distance queries, at most 16 MiB (cs_near.hip.inc)
     return b;
   }
 
@@ -2784,8 +2784,8 @@ struct cs_engine {
   // the raster of cs_agent_field (cs_field.hip.inc): grown to the largest raster asked for, never shrunk
   void* field_scratch = nullptr;
   size_t field_scratch_bytes = 0;
-  // the pair arrays of cs_close_pairs (cs_close_pairs.hip.inc): kept while they need at most PAIRS_SCRATCH_KEEP bytes; a
-  // larger list is allocated for its call and freed before it returns
+  // the lists of cs_close_pairs, cs_agent_clusters and cs_agent_neighbours (PairsScratch, cs_near.hip.inc): kept while
+  // they need at most PAIRS_SCRATCH_KEEP bytes; a larger list is allocated for its call and freed before it returns
   void* pairs_scratch = nullptr;
   size_t pairs_scratch_bytes = 0;
 };

@@ -270,14 +270,15 @@ static int mesh_host_gatherv(cs_mesh* m, const void* mine, size_t bytes, std::ve
 // this process directly), every rank merges the same global table, and each tile maps its agents by binary search in it
 // (k_ids_renumber_ext).  Between two mesh steps no tile holds ghosts, and what the step kernels packed is voided, so the
 // next exchange carries the new ids.  Collective: every rank makes the same calls.
-// merge the ascending runs of v ending at `ends` (pairwise, in place)
-static void mesh_merge_runs(std::vector<uint64_t>& v, std::vector<size_t> ends) {
+// merge the runs of v ending at `ends`, each ascending under `less` (pairwise, in place)
+template <class T, class Less = std::less<T>>
+static void mesh_merge_runs(std::vector<T>& v, std::vector<size_t> ends, Less less = Less()) {
   while (ends.size() > 1) {
     std::vector<size_t> next;
     for (size_t i = 0; i < ends.size(); i += 2) {
       if (i + 1 < ends.size()) {
         const size_t b = i ? ends[i - 1] : 0;
-        std::inplace_merge(v.begin() + (long)b, v.begin() + (long)ends[i], v.begin() + (long)ends[i + 1]);
+        std::inplace_merge(v.begin() + (long)b, v.begin() + (long)ends[i], v.begin() + (long)ends[i + 1], less);
       }
       next.push_back(ends[std::min(i + 1, ends.size() - 1)]);
     }

@@ -1,15 +1,14 @@
 // cs_neighbours.hip.inc — what surrounds each agent, between steps: how many others stand within a distance of it and
 // which of them is the closest (include/crowdstep_state.h, "Neighbours of each agent between steps").  Part of the single
-// translation unit crowdstep_hip.hip (included there, after cs_clusters.hip.inc; it uses pairs_self / pairs_in_grid,
-// the block helpers, k_pairs_hist / k_pairs_scatter and PairsScratch of cs_close_pairs.hip.inc, clusters_sort of
-// cs_clusters.hip.inc, sel_pred of cs_select.hip.inc and k_ids_scan of cs_kernels_ids.hip.inc, none of which it changes).
+// translation unit crowdstep_hip.hip (included there, after cs_clusters.hip.inc; it uses the walk, the band, the cross
+// loop, the block helpers and PairsScratch of cs_near.hip.inc and clusters_sort of cs_clusters.hip.inc, none of which it
+// changes).
 //
 //   K_neighbours   k_neighbours<FORM>, one lane per slot of the CELL-SORTED arrays.  pairs_self judges the lane's own
-//                  agent with role A = subjects and role B = others; only a subject goes on.  The walk is that of
-//                  pairs_walk (the same rectangle of reach cells, the same per-row runs of cell_start, the same f64
-//                  expression), but over ALL candidate slots j != i: the statistic is per subject, so nothing is judged
-//                  "once per pair".  A candidate that passes the distance test is then checked for the grid's rectangle
-//                  and, only then, for the others role.  A hit raises the lane's count and replaces (best d2, best id)
+//                  agent with role A = subjects and role B = others; only a subject goes on.  It walks (near_walk)
+//                  over ALL candidate slots j != i: the statistic is per subject, so nothing is judged "once per pair".
+//                  A candidate that passes the distance test is then checked for the grid's rectangle and, only then,
+//                  for the others role (near_roles).  A hit raises the lane's count and replaces (best d2, best id)
 //                  when (d2, id) is lexicographically smaller, so the row does not depend on the order of the walk.
 //   forms          NEIGH_COUNT  the number of subjects with count >= min_count: summed over the wave by shuffles, over
 //                               the workgroup in LDS, ONE 64-bit atomic per workgroup (pairs_block_tally); no row exists.
@@ -17,15 +16,13 @@
 //                               a key (id << 32 | row) and the 24-byte row (count, nearest, d2).
 //                  NEIGH_STAGE  (mesh) every slot writes its subject id (or none) and its row at its own slot, for the
 //                               merge with what lies behind the cuts; k_neighbours_report applies min_count afterwards.
-//   order          the radix passes of the pairs over the id word of the keys (clusters_sort: k_pairs_hist / k_ids_scan /
-//                  k_pairs_scatter; passes above the bits of the largest reported id are skipped), then
-//                  k_neighbours_gather writes the first min(count, cap) rows as cs_neighbour_stat in key order.  The
-//                  host maps id and nearest to external ids and does nothing else per row.
-//   mesh           k_neighbours_band, the twin of k_pairs_band that also notes the slot of every record, exports
-//                  (id, x, y, role bits, tile) of the participants within reach of an edge that has a neighbour tile;
-//                  k_neighbours_cross tests a tile's band SUBJECTS against the gathered band OTHERS of every other tile,
-//                  LDS-tiled over the foreign records, the same f64 expression, and merges count and (d2, id) into the
-//                  subject's staged row: one lane owns one subject, so the merge needs no atomic.
+//   order          the radix passes over the id word of the keys (clusters_sort), then k_neighbours_gather writes the
+//                  first min(count, cap) rows as cs_neighbour_stat in key order.  The host maps id and nearest to
+//                  external ids and does nothing else per row.
+//   mesh           k_pairs_band, which here also notes the slot of every record, exports (id, x, y, role bits, tile) of
+//                  the participants in the band (bit 0 a subject, bit 1 an other); k_neighbours_cross tests a tile's
+//                  band SUBJECTS against the gathered band OTHERS of every other tile (near_cross) and merges count and
+//                  (d2, id) into the subject's staged row: one lane owns one subject, so the merge needs no atomic.
 //
 // Scratch: the count-only form needs 256 bytes of the by-id scratch.  The listing (two key arrays, the rows, the ordered
 // rows, the digit histogram: at most 72 bytes per slot) goes through PairsScratch: kept in cs_engine::pairs_scratch
@@ -52,6 +49,8 @@ struct NeighStat {
   double d2;
 };
 
+__device__ __forceinline__ NeighStat neigh_none() { return NeighStat{0u, NEIGH_NONE, __builtin_inf()}; }
+
 __device__ __forceinline__ void neigh_take(NeighStat* st, double d2, uint32_t id) {
   ++st->count;
   if (d2 < st->d2 || (d2 == st->d2 && id < st->best)) {
@@ -68,53 +67,18 @@ __device__ __forceinline__ NeighRow neigh_row(const NeighStat& st) {
   return r;
 }
 
-// The walk of one subject in slot i: every other q != s with d2 < dist2 (the rectangle and the runs of pairs_walk).
-__device__ __forceinline__ void neigh_walk(const GridDev& g, const AgentArrays& a, uint32_t i, uint32_t limit,
-                                           const uint32_t* __restrict__ cell_start,
-                                           const SelGroupDev* __restrict__ groups, const PairsArgs& P,
-                                           const PairsSelf& s, NeighStat* st) {
-  const long long lo_x = P.owned_only ? g.own_x0 : 0u, hi_x = P.owned_only ? g.own_x1 : g.ny;
-  const long long lo_y = P.owned_only ? g.own_y0 : 0u, hi_y = P.owned_only ? g.own_y1 : g.nx;
-  const long long R = P.reach;
-  const long long xl = max((long long)s.cx - R, lo_x), xh = min((long long)s.cx + R, hi_x - 1);
-  const long long yl = max((long long)s.cy - R, lo_y), yh = min((long long)s.cy + R, hi_y - 1);
-  if (yl > yh) return;
-  for (long long xr = xl; xr <= xh; ++xr) {
-    const uint32_t rowbase = (uint32_t)xr * g.nx;  // (below ncells, which fits 32 bits)
-    const uint32_t b = cell_start[rowbase + (uint32_t)yl];
-    const uint32_t e = min(cell_start[rowbase + (uint32_t)yh + 1u], limit);  // (index <= ncells: the table has ncells + 1)
-    const double bx = (double)((uint64_t)g.org_x + (uint64_t)xr) * P.cell_size;
-    for (uint32_t j = b; j < e; ++j) {
-      if (j == i) continue;
-      const uint32_t cyj = a.cell[j] - rowbase;
-      if (cyj > (uint32_t)yh) continue;  // (a slot that is not of this row's run: cannot happen in sorted arrays)
-      const float2 off = a.off[j];
-      const double xq = P.off_x + (bx + (double)off.x);
-      const double yq = P.off_y + ((double)((uint64_t)g.org_y + cyj) * P.cell_size + (double)off.y);
-      const double dx = s.x - xq, dy = s.y - yq;
-      const double d2 = dx * dx + dy * dy;
-      if (!(d2 < P.dist2)) continue;
-      if (!pairs_in_grid(P, xq, yq)) continue;
-      if (P.roles) {
-        const uint32_t meta = a.meta[j];
-        const uint32_t grp = meta_group(g, meta);
-        if (grp >= P.n_groups) continue;
-        if (P.roles & 2u) {
-          const SelGroupDev gq = groups[grp];
-          const uint32_t wp = meta_waypoint(g, meta);
-          double vx = 0.0, vy = 0.0;
-          if (P.want_vel) {
-            const float2 v = a.vel[j];
-            vx = (double)v.x;
-            vy = (double)v.y;
-          }
-          if (!sel_pred(P.b, xq, yq, vx, vy, wp, gq.sink, gq.hlp, gq.lp)) continue;
-        }
-      }
-      neigh_take(st, d2, a.id[j]);
-    }
+// What a subject in slot i does on its walk: every other q != s in reach that is inside the grid and an other.
+struct NeighVisit {
+  const SelGroupDev* groups;
+  uint32_t i;
+  NeighStat* st;
+  __device__ __forceinline__ bool take(const AgentArrays&, uint32_t j) { return j != i; }
+  __device__ __forceinline__ void hit(const GridDev& g, const AgentArrays& a, const PairsArgs& P, uint32_t j, double xq,
+                                      double yq, double d2) {
+    if (!pairs_in_grid(P, xq, yq)) return;
+    if (!P.roles || (near_roles(g, a, j, groups, P, xq, yq, 2u) & 2u)) neigh_take(st, d2, a.id[j]);
   }
-}
+};
 
 // K_neighbours.  NEIGH_COUNT: hdr[0] += the reported subjects.  NEIGH_LIST: hdr[1] is the cursor of the list, the low
 // word of hdr[2] the largest id listed; keys and rows have room for `cap` entries (the host gives one per slot).
@@ -129,11 +93,9 @@ __global__ void __launch_bounds__(PAIRS_BLOCK)
   const uint32_t i = blockIdx.x * PAIRS_BLOCK + threadIdx.x;
   PairsSelf s;
   const bool subject = pairs_self(g, a, i, limit, groups, P, &s) && s.ra;
-  NeighStat st;
-  st.count = 0u;
-  st.best = NEIGH_NONE;
-  st.d2 = __builtin_inf();
-  if (subject && P.dist2 > 0.0) neigh_walk(g, a, i, limit, cell_start, groups, P, s, &st);  // (distance 0: strict)
+  NeighStat st = neigh_none();
+  NeighVisit v{groups, i, &st};
+  if (subject && P.dist2 > 0.0) near_walk(g, a, limit, cell_start, P, s.x, s.y, s.cx, s.cy, v);  // (distance 0: strict)
   if (FORM == NEIGH_STAGE) {
     if (i < n_ub) {
       stage_id[i] = subject ? s.id : NEIGH_NONE;
@@ -189,46 +151,17 @@ __global__ void __launch_bounds__(PAIRS_BLOCK)
   out[k] = o;
 }
 
-// The band of a tile, the twin of k_pairs_band (the same rule, the same record: bit 0 a subject, bit 1 an other) that
-// also notes the slot of every record, where its staged row lies.  One atomic per wave; records beyond cap are dropped
-// (the host gives room for every slot).
-__global__ void __launch_bounds__(PAIRS_BLOCK)
-    k_neighbours_band(GridDev g, AgentArrays a, uint32_t n_ub, const uint32_t* __restrict__ cell_start,
-                      const SelGroupDev* __restrict__ groups, PairsArgs P, uint32_t edges, uint32_t tile_index,
-                      PairsBandRec* __restrict__ out, uint32_t* __restrict__ out_slot, uint32_t cap,
-                      uint32_t* __restrict__ count) {
-  const uint32_t limit = min(n_ub, cell_start[g.ncells]);
-  const uint32_t i = blockIdx.x * PAIRS_BLOCK + threadIdx.x;
-  PairsSelf s;
-  bool hit = pairs_self(g, a, i, limit, groups, P, &s);
-  if (hit) {
-    const unsigned long long R = P.reach;
-    hit = ((edges & 1u) && (unsigned long long)s.cx < g.own_x0 + R) || ((edges & 2u) && s.cx + R >= g.own_x1) ||
-          ((edges & 4u) && (unsigned long long)s.cy < g.own_y0 + R) || ((edges & 8u) && s.cy + R >= g.own_y1);
+// What a band subject does with a foreign record in reach: the others among them count.
+struct NeighCrossVisit {
+  NeighStat* st;
+  __device__ __forceinline__ void hit(const PairsBandRec&, const PairsBandRec& q, double d2) {
+    if (q.bits & 2u) neigh_take(st, d2, q.id);
   }
-  const unsigned long long m = __ballot(hit);
-  if (!m) return;
-  const uint32_t lane = __lane_id();
-  const int first = __ffsll((long long)m) - 1;
-  uint32_t base = 0;
-  if ((int)lane == first) base = atomicAdd(count, (uint32_t)__popcll(m));
-  base = __shfl(base, first, 64);
-  if (!hit) return;
-  const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  if (at >= cap) return;
-  PairsBandRec r;
-  r.x = s.x;
-  r.y = s.y;
-  r.id = s.id;
-  r.bits = (s.ra ? 1u : 0u) | (s.rb ? 2u : 0u) | (tile_index << 2);
-  out[at] = r;
-  out_slot[at] = i;
-}
+};
 
 // One lane per band record of the local tile; the subjects among them against the n_f foreign OTHERS (records of other
-// tiles with bit 1, chosen by the host), staged PAIRS_BLOCK at a time in LDS (6 KiB; every lane of a wave reads the
-// same staged record: a broadcast).  Every lane of the workgroup runs the loop.  What a subject finds is merged into
-// its staged row: its slot is this lane's alone.
+// tiles with bit 1, chosen by the host) through near_cross (s_f: 6 KiB).  What a subject finds is merged into its
+// staged row: its slot is this lane's alone.
 __global__ void __launch_bounds__(PAIRS_BLOCK)
     k_neighbours_cross(const PairsBandRec* __restrict__ local, const uint32_t* __restrict__ local_slot, uint32_t n_l,
                        const PairsBandRec* __restrict__ foreign, uint32_t n_f, double dist2, NeighRow* __restrict__ rows,
@@ -238,25 +171,9 @@ __global__ void __launch_bounds__(PAIRS_BLOCK)
   PairsBandRec me = {};
   if (i < n_l) me = local[i];
   const bool live = i < n_l && (me.bits & 1u);
-  NeighStat st;
-  st.count = 0u;
-  st.best = NEIGH_NONE;
-  st.d2 = __builtin_inf();
-  for (uint32_t base = 0; base < n_f; base += PAIRS_BLOCK) {
-    __syncthreads();  // (the chunk before is read)
-    if (base + threadIdx.x < n_f) s_f[threadIdx.x] = foreign[base + threadIdx.x];
-    __syncthreads();
-    const uint32_t m = min(PAIRS_BLOCK, n_f - base);
-    if (!live) continue;
-    for (uint32_t k = 0; k < m; ++k) {
-      const PairsBandRec q = s_f[k];
-      const double dx = me.x - q.x, dy = me.y - q.y;
-      const double d2 = dx * dx + dy * dy;
-      if (!(d2 < dist2)) continue;
-      if (!(q.bits & 2u)) continue;
-      neigh_take(&st, d2, q.id);
-    }
-  }
+  NeighStat st = neigh_none();
+  NeighCrossVisit v{&st};
+  near_cross(me, live, foreign, n_f, dist2, s_f, v);
   if (!live || !st.count) return;
   const uint32_t slot = local_slot[i];
   if (slot >= n_rows) return;
@@ -273,10 +190,7 @@ namespace {
 
 // a NaN or negative distance, a selection cs_select_agents refuses (3)
 int neigh_check(std::string* error, double distance, const cs_selection* subjects, const cs_selection* others) {
-  if (!(distance >= 0.0)) {
-    *error = "agent_neighbours: the distance is NaN or negative";
-    return 3;
-  }
+  if (int rc = near_check_distance(error, distance, "agent_neighbours")) return rc;
   if (subjects)
     if (int rc = sel_check(error, subjects, "agent_neighbours")) return rc;
   if (others)
@@ -285,21 +199,6 @@ int neigh_check(std::string* error, double distance, const cs_selection* subject
 }
 
 bool neigh_by_id(const cs_neighbour_stat& l, const cs_neighbour_stat& r) { return l.id < r.id; }
-
-// merge the ascending runs of v ending at `ends` (pairwise, in place): pairs_merge_runs for rows
-void neigh_merge_runs(std::vector<cs_neighbour_stat>& v, std::vector<size_t> ends) {
-  while (ends.size() > 1) {
-    std::vector<size_t> next;
-    for (size_t i = 0; i < ends.size(); i += 2) {
-      if (i + 1 < ends.size()) {
-        const size_t b = i ? ends[i - 1] : 0;
-        std::inplace_merge(v.begin() + (long)b, v.begin() + (long)ends[i], v.begin() + (long)ends[i + 1], neigh_by_id);
-      }
-      next.push_back(ends[std::min(i + 1, ends.size() - 1)]);
-    }
-    ends.swap(next);
-  }
-}
 
 // the arrays of one listing over n slots, in one allocation through PairsScratch
 struct NeighArrays {
@@ -358,10 +257,9 @@ int neigh_run(cs_engine* e, const PairsArgs& P, uint64_t min_count, size_t want,
                        (NeighRow*)nullptr, (uint32_t*)nullptr, 0u);
     HIP_OK_E(e, hipGetLastError());
     unsigned long long found = 0;
-    HIP_OK_E(e, hipMemcpyAsync(&found, hdr, sizeof found, hipMemcpyDeviceToHost, e->stream));
-    HIP_OK_E(e, hipStreamSynchronize(e->stream));
+    const int rc = pairs_read_count(e, hdr, &found);
     *count = found;
-    return 0;
+    return rc;
   }
   PairsScratch sc(e);
   NeighArrays A;
@@ -370,9 +268,8 @@ int neigh_run(cs_engine* e, const PairsArgs& P, uint64_t min_count, size_t want,
                      e->cell_start, e->sel_groups_dev, P, (unsigned long long)min_count, hdr, A.keys, A.rows, (uint32_t*)nullptr,
                      n);
   HIP_OK_E(e, hipGetLastError());
-  unsigned long long back[3] = {0, 0, 0};
-  HIP_OK_E(e, hipMemcpyAsync(back, hdr, sizeof back, hipMemcpyDeviceToHost, e->stream));
-  HIP_OK_E(e, hipStreamSynchronize(e->stream));
+  unsigned long long back[3];
+  if (int rc = pairs_read_header(e, hdr, back)) return rc;
   if (back[1] > n) {
     e->error = "agent_neighbours: more rows than slots";
     return 90;
@@ -444,23 +341,8 @@ int neigh_stage(cs_engine* e, const PairsArgs& P, uint32_t edges, uint32_t tile_
     HIP_OK_E(e, hipStreamSynchronize(e->stream));
     return 0;
   }
-  HIP_OK_E(e, hipMemsetAsync(d_count, 0, sizeof(uint32_t), e->stream));
-  hipLaunchKernelGGL(k_neighbours_band, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n, e->cell_start,
-                     e->sel_groups_dev, P, edges, tile_index, h->band, h->band_slot, n, d_count);
-  HIP_OK_E(e, hipGetLastError());
-  uint32_t found = 0;
-  HIP_OK_E(e, hipMemcpyAsync(&found, d_count, sizeof found, hipMemcpyDeviceToHost, e->stream));
-  HIP_OK_E(e, hipStreamSynchronize(e->stream));
-  if (found > n) {
-    e->error = "agent_neighbours: more band records than slots";
-    return 90;
-  }
-  h->n_band = found;
-  band->resize(found);
-  if (found) {
-    HIP_OK_E(e, hipMemcpyAsync(band->data(), h->band, (size_t)found * sizeof(PairsBandRec), hipMemcpyDeviceToHost, e->stream));
-    HIP_OK_E(e, hipStreamSynchronize(e->stream));
-  }
+  if (int rc = pairs_band_run(e, P, edges, tile_index, d_count, h->band, h->band_slot, "agent_neighbours", band)) return rc;
+  h->n_band = (uint32_t)band->size();
   return 0;
 }
 
@@ -495,10 +377,9 @@ int neigh_report(NeighHold* h, uint64_t min_count, size_t want, std::vector<cs_n
                        (unsigned long long)min_count, hdr, (unsigned long long*)nullptr, 0u);
     HIP_OK_E(e, hipGetLastError());
     unsigned long long found = 0;
-    HIP_OK_E(e, hipMemcpyAsync(&found, hdr, sizeof found, hipMemcpyDeviceToHost, e->stream));
-    HIP_OK_E(e, hipStreamSynchronize(e->stream));
+    const int rc = pairs_read_count(e, hdr, &found);
     *count = found;
-    return 0;
+    return rc;
   }
   PairsScratch sc(e);
   NeighArrays A;
@@ -506,9 +387,8 @@ int neigh_report(NeighHold* h, uint64_t min_count, size_t want, std::vector<cs_n
   hipLaunchKernelGGL(k_neighbours_report<true>, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, h->stage_id, h->rows, n,
                      (unsigned long long)min_count, hdr, A.keys, n);
   HIP_OK_E(e, hipGetLastError());
-  unsigned long long back[3] = {0, 0, 0};
-  HIP_OK_E(e, hipMemcpyAsync(back, hdr, sizeof back, hipMemcpyDeviceToHost, e->stream));
-  HIP_OK_E(e, hipStreamSynchronize(e->stream));
+  unsigned long long back[3];
+  if (int rc = pairs_read_header(e, hdr, back)) return rc;
   if (back[1] > n) {
     e->error = "agent_neighbours: more rows than slots";
     return 90;
@@ -543,10 +423,7 @@ size_t cs_mesh_agent_neighbours(cs_mesh* m, double distance, const cs_selection*
   if (!m) return SIZE_MAX;
   if (m->dead()) return SIZE_MAX;
   if (neigh_check(&m->error, distance, subjects, others)) return SIZE_MAX;
-  if (m->n_tiles() > 1u && distance > (double)m->halo * m->grid.cell_size) {
-    m->error = "agent_neighbours: on a mesh of more than one tile the distance is at most halo_cells * cell_size";
-    return SIZE_MAX;
-  }
+  if (near_check_mesh_distance(m, distance, "agent_neighbours")) return SIZE_MAX;
   if (cs_mesh_synchronize(m)) return SIZE_MAX;
   hipSetDevice(m->device);
   const size_t want = out ? cap : 0u;
@@ -560,47 +437,14 @@ size_t cs_mesh_agent_neighbours(cs_mesh* m, double distance, const cs_selection*
   for (size_t k = 0; k < n_local; ++k) {
     cs_engine* e = m->tiles[k];
     holds[k].e = e;
-    uint32_t edges = 0;
-    if (m->n_tiles() > 1u)
-      for (int d = 0; d < 4; ++d)
-        if (m->neighbour(m->index_of[k], d) >= 0) edges |= 1u << d;  // (CS_DIR_XLO, XHI, YLO, YHI)
     if (!err) err = sel_begin(e);
     const PairsArgs P = pairs_args(e, distance, subjects, others);
-    if (!err) err = neigh_stage(e, P, edges, m->index_of[k], &holds[k], &bands[k]);
+    if (!err) err = neigh_stage(e, P, mesh_tile_edges(m, k), m->index_of[k], &holds[k], &bands[k]);
     if (err && why.empty()) why = cs_last_error(e);
   }
-  // 2. the band records of every tile on every rank: [failed?], then the records as three words each
+  // 2. the band records of every tile on every rank
   std::vector<PairsBandRec> every;
-  if (m->distributed) {
-    std::vector<uint64_t> mine(1, err ? 1u : 0u);
-    if (!err)
-      for (const auto& b : bands) {
-        const size_t at = mine.size();
-        mine.resize(at + 3u * b.size());
-        if (!b.empty()) std::memcpy(&mine[at], b.data(), b.size() * sizeof(PairsBandRec));
-      }
-    std::vector<std::vector<unsigned char>> parts;
-    if (int rc = mesh_host_gatherv(m, mine.data(), mine.size() * sizeof(uint64_t), parts)) {
-      m->poison(rc, m->error);
-      return SIZE_MAX;
-    }
-    for (const auto& part : parts) {
-      uint64_t failed = 1u;
-      if (part.size() >= sizeof failed) std::memcpy(&failed, part.data(), sizeof failed);
-      if (failed || (part.size() - sizeof(uint64_t)) % sizeof(PairsBandRec)) {
-        if (!err) {
-          err = 90;
-          why = "a tile of another rank failed while counting neighbours";
-        }
-        continue;
-      }
-      const size_t k = (part.size() - sizeof(uint64_t)) / sizeof(PairsBandRec), at = every.size();
-      every.resize(at + k);
-      if (k) std::memcpy(&every[at], part.data() + sizeof(uint64_t), k * sizeof(PairsBandRec));
-    }
-  } else {
-    for (const auto& b : bands) every.insert(every.end(), b.begin(), b.end());
-  }
+  if (mesh_gather_bands(m, bands, "a tile of another rank failed while counting neighbours", &err, &why, &every)) return SIZE_MAX;
   // 3. every local tile's band subjects against the band others of every other tile, merged on the device; then
   //    min_count, the order and the download of each tile's run
   uint64_t total = 0;
@@ -620,7 +464,7 @@ size_t cs_mesh_agent_neighbours(cs_mesh* m, double distance, const cs_selection*
     all.insert(all.end(), part.begin(), part.end());
     ends.push_back(all.size());
   }
-  neigh_merge_runs(all, ends);
+  mesh_merge_runs(all, ends, neigh_by_id);
   if (all.size() > want) all.resize(want);
   // 4. the rows (or only the counts) of every rank: [0 ok / 1 failed, count, n listed, rows as four words each]
   if (m->distributed) {
@@ -654,7 +498,7 @@ size_t cs_mesh_agent_neighbours(cs_mesh* m, double distance, const cs_selection*
       if (n) std::memcpy(&all[at], part.data() + sizeof head, n * sizeof(cs_neighbour_stat));
       ends.push_back(all.size());
     }
-    neigh_merge_runs(all, ends);
+    mesh_merge_runs(all, ends, neigh_by_id);
     if (all.size() > want) all.resize(want);
   }
   if (err) {
