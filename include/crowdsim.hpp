@@ -539,6 +539,30 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
     return n;
   }
+  // Who comes close to whom in the near future (cs_encounters, include/crowdstep_state.h "Encounters between steps"): the
+  // pairs now closer than `range` whose closest approach within `horizon`, both keeping their velocity, is closer than
+  // `distance`: rows (a, b, t, d2) with a < b, ascending, t and d2 bit for bit.  `a`, `b`: the two roles (null:
+  // everyone).  `limit`: at most that many rows (the first ones); a listing of more than CS_PAIRS_MAX rows throws,
+  // count_encounters has no limit.
+  std::vector<cs_encounter> encounters(double distance, double horizon, double range, const cs_selection* a = nullptr,
+                                       const cs_selection* b = nullptr, std::size_t limit = SIZE_MAX) {
+    std::vector<cs_encounter> out;
+    const uint64_t count = count_encounters(distance, horizon, range, a, b);
+    std::size_t cap = (std::size_t)std::min<uint64_t>(count, limit);
+    if (!cap) return out;
+    if (count > CS_PAIRS_MAX) cap = 1;  // (refused by the library, with its message: no room is made for it here)
+    out.resize(cap);
+    const std::size_t n = cs_encounters(engine_, distance, horizon, range, a, b, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  uint64_t count_encounters(double distance, double horizon, double range, const cs_selection* a = nullptr,
+                            const cs_selection* b = nullptr) {
+    const std::size_t n = cs_encounters(engine_, distance, horizon, range, a, b, nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return n;
+  }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
     std::vector<AgentId> ids(cs_agent_count(engine_));
@@ -869,6 +893,30 @@ class TiledSimulation {
   uint64_t count_agents_with_neighbours(double distance, const cs_selection* subjects = nullptr,
                                         const cs_selection* others = nullptr, uint64_t min_count = 1) {
     const std::size_t n = cs_mesh_agent_neighbours(mesh_, distance, subjects, others, min_count, nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return n;
+  }
+  // Who comes close to whom in the near future (cs_mesh_encounters, include/crowdstep_state.h "Encounters between steps"): the
+  // pairs now closer than `range` whose closest approach within `horizon`, both keeping their velocity, is closer than
+  // `distance`: rows (a, b, t, d2) with a < b, ascending, t and d2 bit for bit.  `a`, `b`: the two roles (null:
+  // everyone).  `limit`: at most that many rows (the first ones); a listing of more than CS_PAIRS_MAX rows throws,
+  // count_encounters has no limit.
+  std::vector<cs_encounter> encounters(double distance, double horizon, double range, const cs_selection* a = nullptr,
+                                       const cs_selection* b = nullptr, std::size_t limit = SIZE_MAX) {
+    std::vector<cs_encounter> out;
+    const uint64_t count = count_encounters(distance, horizon, range, a, b);
+    std::size_t cap = (std::size_t)std::min<uint64_t>(count, limit);
+    if (!cap) return out;
+    if (count > CS_PAIRS_MAX) cap = 1;  // (refused by the library, with its message: no room is made for it here)
+    out.resize(cap);
+    const std::size_t n = cs_mesh_encounters(mesh_, distance, horizon, range, a, b, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  uint64_t count_encounters(double distance, double horizon, double range, const cs_selection* a = nullptr,
+                            const cs_selection* b = nullptr) {
+    const std::size_t n = cs_mesh_encounters(mesh_, distance, horizon, range, a, b, nullptr, 0);
     if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
     return n;
   }

@@ -218,6 +218,45 @@
  *     alone; nothing is renumbered.  The call may sort the arrays by cell, as the spatial queries do: the next step runs
  *     to the same bytes as on an engine that never made the call.  The device scratch of a call is kept while it is at
  *     most 16 MiB (the scratch of cs_close_pairs, part of cs_device_bytes); a larger one is freed before the call returns.
+ *
+ * Encounters between steps ("Encounters between steps"): the questions about the NEAR FUTURE of two
+ * agents: which pedestrians will come within 0.5 m of this robot in the next 3 s, how soon and how close; the same over
+ * all pairs for a conflict monitor, a near-miss statistic, a door interlock.  cs_encounters answers with the closest
+ * approach of every pair within a horizon, both agents keeping the velocity they have now (the time to closest approach
+ * the Zanlungo planner is built on); nothing of the crowd comes to the host but the rows asked for.
+ *   - An agent is the record cs_read_agents returns for it at that moment: x, y the reported f64 position, vx, vy the f32
+ *     velocity widened to f64.
+ *   - Who TAKES PART and the roles sel_a / sel_b are exactly those of cs_close_pairs: a finite position inside the grid's
+ *     own rectangle (on a tile engine and on a mesh the GLOBAL grid's), owned agents only on a tile whose arrays hold
+ *     ghosts, the selections judged as for cs_select_agents, NULL: everyone; a pair is reported iff
+ *     (A(p) && B(q)) || (A(q) && B(p)).
+ *   - For two participants p and q, every operation one f64 operation rounded once (no contraction, no reciprocal, no f32
+ *     pre-reject; the division is the correctly rounded one):
+ *         rx = x_q - x_p        ry = y_q - y_p
+ *         wx = vx_q - vx_p      wy = vy_q - vy_p
+ *         d2 = rx*rx + ry*ry                      IN RANGE   iff d2 < range*range   (the left-hand side of cs_close_pairs)
+ *         ww = wx*wx + wy*wy    rw = rx*wx + ry*wy
+ *         t  = 0                       if !(rw < 0)       (not approaching; equal velocities; a NaN)
+ *         t  = -rw / ww, then horizon if !(t < horizon)   otherwise
+ *         cx = rx + wx*t        cy = ry + wy*t
+ *         m2 = cx*cx + cy*cy                      ENCOUNTER  iff in range && m2 < distance*distance
+ *     Swapping p and q negates r, w and c exactly, so t, d2 and m2 are the same bits either way: the answer depends
+ *     neither on the order of the slots nor on tiles.  Non-finite velocities fall wherever IEEE puts them
+ *     (cs_write_agents refuses them).
+ *   - horizon = 0: exactly the pairs of cs_close_pairs(min(distance, range)), with m2 == d2.  distance = +inf: every
+ *     in-range pair with a finite m2.  range = 0 or distance = 0: none.  horizon = +inf and range = +inf are allowed (on
+ *     one engine; a mesh of more than one tile refuses a range above halo_cells * cell_size).
+ *   - The answer: every encounter once, as a cs_encounter (a, b, t, d2) with a < b (external ids under CS_CFG_WIDE_IDS),
+ *     t and d2 = m2 bit for bit, in ascending order of (a, b).  The call returns the full count and writes the first
+ *     min(count, cap) rows, and nothing beyond them.
+ *   - out == NULL or cap == 0: the 64-bit count only, from one pass that materialises nothing.
+ *   - With cap > 0 a count above CS_PAIRS_MAX is refused (SIZE_MAX, "too many encounters to list", the engine usable).
+ *   - Refused with SIZE_MAX, nothing written, the engine or mesh usable: a NaN or negative distance, horizon or range, a
+ *     selection cs_select_agents refuses, and on a mesh of more than one tile a range above halo_cells * cell_size.
+ *   - Queued steps complete first and a failure of one of them is the call's; no events; the last step report is left
+ *     alone; nothing is renumbered.  The call may sort the arrays by cell, as the spatial queries do: the next step runs
+ *     to the same bytes as on an engine that never made the call.  The device scratch of a listing is kept while it is at
+ *     most 16 MiB (the scratch of cs_close_pairs, part of cs_device_bytes); a larger one is freed before the call returns.
  */
 #ifndef CROWDSTEP_STATE_H
 #define CROWDSTEP_STATE_H
@@ -404,6 +443,28 @@ size_t cs_agent_neighbours(cs_engine*, double distance, const cs_selection* subj
  * every rank return SIZE_MAX. */
 size_t cs_mesh_agent_neighbours(cs_mesh*, double distance, const cs_selection* subjects, const cs_selection* others,
                                 uint64_t min_count, cs_neighbour_stat* out, size_t cap);
+
+typedef struct cs_encounter {   /* 32 bytes */
+  uint64_t a, b;        /* the two agents, a < b                                           */
+  double   t;           /* the time of their closest approach, in [0, horizon]: bit for bit */
+  double   d2;          /* their squared distance then (m2 of the rule): bit for bit        */
+} cs_encounter;
+/* The pairs of agents now closer than `range` that come closer than `distance` within `horizon`, both keeping their
+ * velocity, ascending by (a, b).  Returns the full count and writes min(count, cap) rows (the first ones); out == NULL or
+ * cap == 0: the count only (64-bit on the device, no limit).  sel_a / sel_b: the two roles of a pair, NULL: everyone.
+ * SIZE_MAX on error. */
+size_t cs_encounters(cs_engine*, double distance, double horizon, double range, const cs_selection* sel_a,
+                     const cs_selection* sel_b, cs_encounter* out, size_t cap);
+/* The same on a mesh.  Collective: every rank passes the same arguments and gets the whole answer, byte for byte the
+ * single engine's.  On a mesh of more than one tile `range` is at most halo_cells * cell_size (so +inf is refused there).
+ * The scheme is that of cs_mesh_close_pairs, the band record also carrying the widened velocity (40 bytes): no halo
+ * exchange is made and the step's own exchange state is left as it is; one gather brings the band records to every rank,
+ * each rank tests its tiles' band agents against the records of the tiles with a higher index (every cross-tile pair
+ * exactly once), one more gather moves the rows (the count-only form: the counts), and every rank merges the sorted runs.
+ * The number of collectives depends neither on the crowd nor on the answer.  A tile that fails makes every rank return
+ * SIZE_MAX. */
+size_t cs_mesh_encounters(cs_mesh*, double distance, double horizon, double range, const cs_selection* sel_a,
+                          const cs_selection* sel_b, cs_encounter* out, size_t cap);
 
 #ifdef __cplusplus
 }

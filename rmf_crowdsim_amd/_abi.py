@@ -291,12 +291,19 @@ class NeighbourStat(C.Structure):
     _fields_ = [("id", C.c_uint64), ("count", C.c_uint64), ("nearest", C.c_uint64), ("nearest_d2", C.c_double)]
 
 
+class Encounter(C.Structure):
+    """cs_encounter: one row of cs_encounters, a < b (include/crowdstep_state.h)"""
+    _fields_ = [("a", C.c_uint64), ("b", C.c_uint64), ("t", C.c_double), ("d2", C.c_double)]
+
+
 _PAIRS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.POINTER(IdPair), C.POINTER(C.c_double),
                C.c_size_t]
 _CLUSTERS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                   C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(Cluster), C.c_size_t, C.POINTER(C.c_size_t)]
 _NEIGHBOURS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.c_uint64,
                     C.POINTER(NeighbourStat), C.c_size_t]
+_ENCOUNTERS_ARGS = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.POINTER(Selection), C.POINTER(Selection),
+                    C.POINTER(Encounter), C.c_size_t]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -329,6 +336,8 @@ STATE_SYMBOLS = {
     "cs_mesh_agent_clusters": (C.c_int, list(_CLUSTERS_ARGS)),
     "cs_agent_neighbours": (C.c_size_t, list(_NEIGHBOURS_ARGS)),
     "cs_mesh_agent_neighbours": (C.c_size_t, list(_NEIGHBOURS_ARGS)),
+    "cs_encounters": (C.c_size_t, list(_ENCOUNTERS_ARGS)),
+    "cs_mesh_encounters": (C.c_size_t, list(_ENCOUNTERS_ARGS)),
 }
 
 

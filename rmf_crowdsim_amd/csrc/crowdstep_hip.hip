@@ -21,11 +21,12 @@
 //   cs_set_targets.hip.inc    sending agents to goals by id, a batch at a time (the same header)
 //   cs_select.hip.inc         selecting, counting and removing agents by region, owner and state (the same header)
 //   cs_field.hip.inc          rasterising the crowd into a grid (the same header)
-//   cs_near.hip.inc           what the three distance queries below share: the walk over the cells in reach, the band of
+//   cs_near.hip.inc           what the four distance queries below share: the walk over the cells in reach, the band of
 //                             a tile, the cross loop over the bands of other tiles, the block helpers, the sort of a list
 //   cs_close_pairs.hip.inc    the pairs of agents within a distance of one another (the same header)
 //   cs_clusters.hip.inc       the clusters of agents under that distance: union-find on the device (the same header)
 //   cs_neighbours.hip.inc     per agent: how many others within a distance, and the nearest of them (the same header)
+//   cs_encounters.hip.inc     the pairs that come within a distance of one another inside a time horizon (the same header)
 //   this file                 includes + the extern "C" boundary
 //
 // Device state is f32 and CELL-RELATIVE: an agent is (stored cell, offset from
@@ -1265,3 +1266,4 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_close_pairs.hip.inc"
 #include "cs_clusters.hip.inc"
 #include "cs_neighbours.hip.inc"
+#include "cs_encounters.hip.inc"

@@ -733,6 +733,41 @@ def agent_neighbours_of(fn, handle, handle_of, err, distance, subjects, others, 
     return int(n), rows
 
 
+ENCOUNTER_DTYPE = np.dtype([("a", np.uint64), ("b", np.uint64), ("t", np.float64), ("d2", np.float64)])
+assert ENCOUNTER_DTYPE.itemsize == C.sizeof(_abi.Encounter) == 32
+
+
+def encounters_call(fn, handle, distance, horizon, range_, sel_a, sel_b, cap):
+    """cs_encounters / cs_mesh_encounters with room for `cap` rows -> (the full count, or None on error; the first
+    min(count, cap) rows as an ENCOUNTER_DTYPE array).  sel_a / sel_b: an _abi.Selection or None (everyone); cap == 0:
+    the count only."""
+    cap = max(int(cap), 0)
+    rows = np.zeros(max(cap, 1), dtype=ENCOUNTER_DTYPE)
+    got = fn(handle, float(distance), float(horizon), float(range_), C.byref(sel_a) if sel_a is not None else None,
+             C.byref(sel_b) if sel_b is not None else None,
+             rows.ctypes.data_as(C.POINTER(_abi.Encounter)) if cap else None, cap)
+    if got == _SIZE_MAX:
+        return None, rows[:0].copy()
+    return got, rows[:min(got, cap)].copy()
+
+
+def encounters_of(fn, handle, handle_of, err, distance, horizon, range_, a, b, limit):
+    """encounters and count_encounters of Simulation and NativeTileMesh.  limit=None lists every encounter (one counting
+    call first), limit=0 only counts -> (count, rows)"""
+    sel_a = None if a is None else selection_struct(a, handle_of)
+    sel_b = None if b is None else selection_struct(b, handle_of)
+    if limit is None:
+        limit, _ = encounters_call(fn, handle, distance, horizon, range_, sel_a, sel_b, 0)
+        if limit is None:
+            raise err()
+        if limit > _abi.CS_PAIRS_MAX:
+            limit = 1  # (the listing is refused by the library, with its message: no room is made for it here)
+    n, rows = encounters_call(fn, handle, distance, horizon, range_, sel_a, sel_b, limit)
+    if n is None:
+        raise err()
+    return int(n), rows
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -1128,6 +1163,24 @@ class Simulation:
         fn = state_fn(self._lib, self.backend, "cs_agent_neighbours", "agent_neighbours")
         return agent_neighbours_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, subjects,
                                    others, min_count, 0)[0]
+
+    def encounters(self, distance, horizon, range, a=None, b=None, *, limit=None):
+        """Who comes close to whom in the near future, on the device (cs_encounters): the pairs of agents now closer than
+        `range` whose closest approach within the next `horizon` seconds, both keeping the velocity read_agents()
+        reports, is closer than `distance`.  Returns a structured array (a, b, t, d2) with a < b, every encounter once,
+        ascending by (a, b): t the time of the closest approach in [0, horizon] (0: not approaching), d2 the squared
+        distance then, both bit for bit the f64 rule of include/crowdstep_state.h.  `a`, `b`: the two roles of a pair, as
+        for close_pairs.  `limit`: at most that many rows (the first ones); listing more than _abi.CS_PAIRS_MAX rows
+        raises, count_encounters has no limit.  Changes nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_encounters", "encounters")
+        return encounters_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, horizon,
+                             range, a, b, limit)[1]
+
+    def count_encounters(self, distance, horizon, range, a=None, b=None):
+        """len(encounters(distance, horizon, range, a, b)) from one pass that lists nothing, exact whatever its size."""
+        fn = state_fn(self._lib, self.backend, "cs_encounters", "encounters")
+        return encounters_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, horizon,
+                             range, a, b, 0)[0]
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

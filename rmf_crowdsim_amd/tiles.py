@@ -790,6 +790,23 @@ class NativeTileMesh:
         return agent_neighbours_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, subjects, others,
                                    min_count, 0)[0]
 
+    def encounters(self, distance, horizon, range, a=None, b=None, *, limit=None):
+        """Simulation.encounters on the mesh (cs_mesh_encounters): the single engine's answer, byte for byte (collective
+        in the distributed form).  With more than one tile, range <= halo_cells * cell_size.  Every tile lists the
+        encounters among its own agents; the agents near a cut travel as band records with their velocity and are tested
+        across tiles; no halo exchange is made."""
+        from .simulation import encounters_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_encounters", "encounters")
+        return encounters_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, horizon, range, a, b,
+                             limit)[1]
+
+    def count_encounters(self, distance, horizon, range, a=None, b=None):
+        """Simulation.count_encounters on the mesh (collective in the distributed form): only counts travel."""
+        from .simulation import encounters_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_encounters", "encounters")
+        return encounters_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, horizon, range, a, b,
+                             0)[0]
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
