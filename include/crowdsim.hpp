@@ -563,6 +563,25 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
     return n;
   }
+  // What each ray hits first (cs_cast_rays, include/crowdstep_state.h "Rays against the crowd between steps"): every agent
+  // is a disc of `radius`, row k of the answer is the first agent ray k enters and the parameter t where it does (the point
+  // o + u * t, the direction as given), bit for bit; {CS_NO_HIT, +inf} for a ray that hits nobody.  `targets`: who can
+  // be hit (null: everyone).  Line of sight from A to B: o = A, u = B - A, t_max = 1, ignore = A; visible iff the hit is B.
+  std::vector<cs_ray_hit> cast_rays(const cs_ray* rays, std::size_t n, double radius, const cs_selection* targets = nullptr) {
+    std::vector<cs_ray_hit> out(n);
+    const std::size_t hits = cs_cast_rays(engine_, rays, n, radius, targets, out.data());
+    if (hits == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return out;
+  }
+  std::vector<cs_ray_hit> cast_rays(const std::vector<cs_ray>& rays, double radius, const cs_selection* targets = nullptr) {
+    return cast_rays(rays.data(), rays.size(), radius, targets);
+  }
+  // the number of rays of cast_rays(...) that hit somebody; no rows are written
+  std::size_t count_ray_hits(const std::vector<cs_ray>& rays, double radius, const cs_selection* targets = nullptr) {
+    const std::size_t hits = cs_cast_rays(engine_, rays.data(), rays.size(), radius, targets, nullptr);
+    if (hits == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return hits;
+  }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
     std::vector<AgentId> ids(cs_agent_count(engine_));
@@ -919,6 +938,25 @@ class TiledSimulation {
     const std::size_t n = cs_mesh_encounters(mesh_, distance, horizon, range, a, b, nullptr, 0);
     if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
     return n;
+  }
+  // What each ray hits first (cs_mesh_cast_rays, include/crowdstep_state.h "Rays against the crowd between steps"): every agent
+  // is a disc of `radius`, row k of the answer is the first agent ray k enters and the parameter t where it does (the point
+  // o + u * t, the direction as given), bit for bit; {CS_NO_HIT, +inf} for a ray that hits nobody.  `targets`: who can
+  // be hit (null: everyone).  Line of sight from A to B: o = A, u = B - A, t_max = 1, ignore = A; visible iff the hit is B.
+  std::vector<cs_ray_hit> cast_rays(const cs_ray* rays, std::size_t n, double radius, const cs_selection* targets = nullptr) {
+    std::vector<cs_ray_hit> out(n);
+    const std::size_t hits = cs_mesh_cast_rays(mesh_, rays, n, radius, targets, out.data());
+    if (hits == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return out;
+  }
+  std::vector<cs_ray_hit> cast_rays(const std::vector<cs_ray>& rays, double radius, const cs_selection* targets = nullptr) {
+    return cast_rays(rays.data(), rays.size(), radius, targets);
+  }
+  // the number of rays of cast_rays(...) that hit somebody; no rows are written
+  std::size_t count_ray_hits(const std::vector<cs_ray>& rays, double radius, const cs_selection* targets = nullptr) {
+    const std::size_t hits = cs_mesh_cast_rays(mesh_, rays.data(), rays.size(), radius, targets, nullptr);
+    if (hits == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return hits;
   }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {

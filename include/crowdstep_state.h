@@ -466,6 +466,63 @@ size_t cs_encounters(cs_engine*, double distance, double horizon, double range, 
 size_t cs_mesh_encounters(cs_mesh*, double distance, double horizon, double range, const cs_selection* sel_a,
                           const cs_selection* sel_b, cs_encounter* out, size_t cap);
 
+/* Rays against the crowd between steps.  A range scan (what does each lidar beam hit first, and how far away), a line of
+ * sight, a free corridor: every agent is a disc of `radius` around the position cs_read_agents reports, and a ray
+ * reports the first disc it enters.
+ *
+ * PARTICIPANTS are the pairs' participants: the agents whose reported position is finite and inside the grid's own
+ * rectangle (on a tile or a mesh: the global one; on a tile engine with ghosts only owned agents).  `targets` (NULL:
+ * everyone) restricts who can be hit; everybody else is transparent.
+ *
+ * THE RULE, for ray (o, u, t_max, ignore) and participant q != ignore at (x_q, y_q), with R2 = radius * radius and
+ * uu = ux*ux + uy*uy, every operation one f64 operation rounded once (no contraction, no reciprocal, the correctly
+ * rounded division and square root):
+ *     rx = x_q - ox;  ry = y_q - oy;  d2 = rx*rx + ry*ry
+ *     if d2 < R2:                    t = +0.0            (the origin stands inside the disc)
+ *     else:
+ *       b  = rx*ux + ry*uy;          miss if !(b > 0)
+ *       cr = rx*uy - ry*ux
+ *       h2 = R2*uu - cr*cr;          miss if !(h2 > 0)   (grazing is a miss)
+ *       t  = (b - sqrt(h2)) / uu;    if t < 0: t = +0.0  (rounding only)
+ *     HIT iff t < t_max
+ * The answer of a ray is the lexicographic minimum of (t, id) over its hits (of two discs entered at the same t the
+ * smaller id), or {CS_NO_HIT, +inf}.  It depends neither on slots nor on tiles.  t is in units of the direction AS GIVEN:
+ * the point of entry is o + u * t, and a direction of length 2 halves t.  t_max == 0 and radius == 0 hit nothing;
+ * t_max = +inf is allowed everywhere, the grid being finite.
+ *
+ * LINE OF SIGHT from agent A to agent B: o = A's position, u = B - A, t_max = 1, ignore = A; B is visible iff the hit is
+ * B (anybody else's disc is entered first otherwise, and a miss means B itself is not a participant or not a target).
+ *
+ * Refused (SIZE_MAX, nothing written, the engine or mesh still usable; the text names the first bad ray): n >
+ * CS_RAYS_MAX, rays == NULL with n > 0, a NaN or negative radius, a ray with a non-finite ox, oy, ux or uy, with uu
+ * outside [2^-100, 2^100] (a zero direction included) or with a NaN or negative t_max, a selection cs_select_agents
+ * refuses.  Queued steps complete first and an Err of one of them is the call's; no events, the last step report is left
+ * alone, nothing is renumbered, and a twin that never asks stays byte-equal. */
+#define CS_NO_HIT   UINT64_MAX
+#define CS_RAYS_MAX (1u << 20)          /* rays of one call */
+typedef struct cs_ray {                 /* 48 bytes */
+  double ox, oy;        /* origin, world coordinates, finite                                   */
+  double ux, uy;        /* direction AS GIVEN (not normalised): the point at t is o + u * t    */
+  double t_max;         /* hits with t < t_max count; >= 0, +inf allowed                       */
+  uint64_t ignore;      /* an agent id this ray passes through (the robot that casts it);
+                           CS_NO_HIT: nobody; an id that is not alive: nobody                  */
+} cs_ray;
+typedef struct cs_ray_hit {             /* 16 bytes */
+  uint64_t id;          /* the first agent hit; CS_NO_HIT: none                                */
+  double   t;           /* its parameter, bit for bit by the rule; +inf when none              */
+} cs_ray_hit;
+/* Casts n rays; row k of `out` (n rows; may be NULL) is the answer of ray k.  Returns the number of rays that hit
+ * something (n == 0: 0), SIZE_MAX on error. */
+size_t cs_cast_rays(cs_engine*, const cs_ray* rays, size_t n, double radius, const cs_selection* targets,
+                    cs_ray_hit* out /* n rows, row k for ray k; may be NULL */);
+/* The same on a mesh.  Collective: every rank passes the same rays and gets the single engine's answer, byte for byte.
+ * No halo exchange is made, there are no band records, and t_max and radius have no limit: every tile casts ALL rays
+ * against the agents it owns and one gather moves n 16-byte rows per rank; every rank takes the lexicographic minimum of
+ * (t, id) per ray.  The number of collectives depends neither on the crowd nor on the answer.  A tile that fails makes
+ * every rank return SIZE_MAX.  The step's exchange state is not touched. */
+size_t cs_mesh_cast_rays(cs_mesh*, const cs_ray* rays, size_t n, double radius, const cs_selection* targets,
+                         cs_ray_hit* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,8 @@ CS_SELECT_MAX = 1024
 CS_FIELD_MAX_CELLS = 4194304
 CS_PAIRS_MAX = 1 << 26
 CS_NO_NEIGHBOUR = 0xFFFFFFFFFFFFFFFF
+CS_NO_HIT = 0xFFFFFFFFFFFFFFFF
+CS_RAYS_MAX = 1 << 20
 
 
 class Selection(C.Structure):
@@ -296,6 +298,17 @@ class Encounter(C.Structure):
     _fields_ = [("a", C.c_uint64), ("b", C.c_uint64), ("t", C.c_double), ("d2", C.c_double)]
 
 
+class Ray(C.Structure):
+    """cs_ray: one ray of cs_cast_rays; the point at t is o + u * t (include/crowdstep_state.h)"""
+    _fields_ = [("ox", C.c_double), ("oy", C.c_double), ("ux", C.c_double), ("uy", C.c_double), ("t_max", C.c_double),
+                ("ignore", C.c_uint64)]
+
+
+class RayHit(C.Structure):
+    """cs_ray_hit: the answer of one ray; id == CS_NO_HIT and t == +inf when it hits nobody"""
+    _fields_ = [("id", C.c_uint64), ("t", C.c_double)]
+
+
 _PAIRS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.POINTER(IdPair), C.POINTER(C.c_double),
                C.c_size_t]
 _CLUSTERS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -304,6 +317,7 @@ _NEIGHBOURS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Sele
                     C.POINTER(NeighbourStat), C.c_size_t]
 _ENCOUNTERS_ARGS = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.POINTER(Selection), C.POINTER(Selection),
                     C.POINTER(Encounter), C.c_size_t]
+_RAYS_ARGS = [C.c_void_p, C.POINTER(Ray), C.c_size_t, C.c_double, C.POINTER(Selection), C.POINTER(RayHit)]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -338,6 +352,8 @@ STATE_SYMBOLS = {
     "cs_mesh_agent_neighbours": (C.c_size_t, list(_NEIGHBOURS_ARGS)),
     "cs_encounters": (C.c_size_t, list(_ENCOUNTERS_ARGS)),
     "cs_mesh_encounters": (C.c_size_t, list(_ENCOUNTERS_ARGS)),
+    "cs_cast_rays": (C.c_size_t, list(_RAYS_ARGS)),
+    "cs_mesh_cast_rays": (C.c_size_t, list(_RAYS_ARGS)),
 }
 
 

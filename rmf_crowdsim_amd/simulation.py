@@ -768,6 +768,42 @@ def encounters_of(fn, handle, handle_of, err, distance, horizon, range_, a, b, l
     return int(n), rows
 
 
+RAY_DTYPE = np.dtype([("ox", np.float64), ("oy", np.float64), ("ux", np.float64), ("uy", np.float64),
+                      ("t_max", np.float64), ("ignore", np.uint64)])
+RAY_HIT_DTYPE = np.dtype([("id", np.uint64), ("t", np.float64)])
+assert RAY_DTYPE.itemsize == C.sizeof(_abi.Ray) == 48 and RAY_HIT_DTYPE.itemsize == C.sizeof(_abi.RayHit) == 16
+
+
+def rays_array(origins, directions, t_max=np.inf, ignore=None):
+    """The RAY_DTYPE array of n rays: origins and directions are (n, 2); t_max and ignore one value for all or one per ray
+    (ignore None: nobody)."""
+    origins = np.asarray(origins, dtype=np.float64).reshape(-1, 2)
+    directions = np.asarray(directions, dtype=np.float64).reshape(-1, 2)
+    if len(origins) != len(directions):
+        raise ValueError("cast_rays: as many directions as origins")
+    rays = np.zeros(len(origins), dtype=RAY_DTYPE)
+    rays["ox"], rays["oy"] = origins[:, 0], origins[:, 1]
+    rays["ux"], rays["uy"] = directions[:, 0], directions[:, 1]
+    rays["t_max"] = np.asarray(t_max, dtype=np.float64)
+    rays["ignore"] = _abi.CS_NO_HIT if ignore is None else np.asarray(ignore, dtype=np.uint64)
+    return rays
+
+
+def cast_rays_of(fn, handle, handle_of, err, rays, radius, targets, want_rows):
+    """cast_rays and count_ray_hits of Simulation and NativeTileMesh -> (the number of rays that hit, the RAY_HIT_DTYPE
+    rows or None)"""
+    sel = None if targets is None else selection_struct(targets, handle_of)
+    rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+    n = len(rays)
+    rows = np.zeros(max(n, 1), dtype=RAY_HIT_DTYPE) if want_rows else None
+    got = fn(handle, rays.ctypes.data_as(C.POINTER(_abi.Ray)) if n else None, n, float(radius),
+             C.byref(sel) if sel is not None else None,
+             rows.ctypes.data_as(C.POINTER(_abi.RayHit)) if want_rows else None)
+    if got == _SIZE_MAX:
+        raise err()
+    return int(got), (rows[:n].copy() if want_rows else None)
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -1181,6 +1217,26 @@ class Simulation:
         fn = state_fn(self._lib, self.backend, "cs_encounters", "encounters")
         return encounters_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, distance, horizon,
                              range, a, b, 0)[0]
+
+    def cast_rays(self, origins, directions, radius, *, t_max=np.inf, ignore=None, targets=None):
+        """What does each ray hit first, on the device (cs_cast_rays): every agent is a disc of `radius` around the
+        position read_agents() reports.  origins, directions: (n, 2) arrays; the point of ray k at t is origin + direction
+        * t, the direction taken AS GIVEN (a unit direction makes t a distance).  t_max (hits with t < t_max count) and
+        ignore (an agent id the ray passes through: the robot that casts it; None: nobody) are one value for all rays or
+        one per ray.  targets: who can be hit (a selection as for select_agents; None: everyone).  Returns a structured
+        array (id, t), row k for ray k: the first agent entered and where, bit for bit the f64 rule of
+        include/crowdstep_state.h, of equal t the smaller id; (_abi.CS_NO_HIT, inf) for a ray that hits nobody.  Line of
+        sight from A to B: origin A, direction B - A, t_max 1, ignore A; B is visible iff the hit is B.  Changes
+        nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_cast_rays", "cast_rays")
+        return cast_rays_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err,
+                            rays_array(origins, directions, t_max, ignore), radius, targets, True)[1]
+
+    def count_ray_hits(self, origins, directions, radius, *, t_max=np.inf, ignore=None, targets=None):
+        """The number of rays of cast_rays(...) that hit somebody; no rows are written."""
+        fn = state_fn(self._lib, self.backend, "cs_cast_rays", "cast_rays")
+        return cast_rays_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err,
+                            rays_array(origins, directions, t_max, ignore), radius, targets, False)[0]
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

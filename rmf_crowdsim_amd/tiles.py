@@ -807,6 +807,22 @@ class NativeTileMesh:
         return encounters_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, distance, horizon, range, a, b,
                              0)[0]
 
+    def cast_rays(self, origins, directions, radius, *, t_max=float("inf"), ignore=None, targets=None):
+        """Simulation.cast_rays on the mesh (cs_mesh_cast_rays): the single engine's answer, byte for byte (collective in
+        the distributed form).  Every tile casts all rays against the agents it owns and the rows are merged by the
+        minimum of (t, id); t_max and radius have no limit and no halo exchange is made."""
+        from .simulation import cast_rays_of, rays_array, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_cast_rays", "cast_rays")
+        return cast_rays_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err,
+                            rays_array(origins, directions, t_max, ignore), radius, targets, True)[1]
+
+    def count_ray_hits(self, origins, directions, radius, *, t_max=float("inf"), ignore=None, targets=None):
+        """Simulation.count_ray_hits on the mesh (collective in the distributed form)."""
+        from .simulation import cast_rays_of, rays_array, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_cast_rays", "cast_rays")
+        return cast_rays_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err,
+                            rays_array(origins, directions, t_max, ignore), radius, targets, False)[0]
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
