@@ -1,0 +1,485 @@
+"""What tests/test_gpu_queries_odd_grids.py and its mesh twin share: the grids none of the between-step query tests runs
+on (one-sided, one cell wide or high, two-launch scans, cell indices near 2^31, a cell size whose multiples are inexact,
+an offset that dwarfs the cell) and one function per query family that asks the engine (or a mesh) and compares the
+answer with the numpy restatement on `records`, its OWN read_agents(), exactly as the query tests do on their square
+grids of 2 m cells.  Ids, counts, orders and the bits of every f64 are exact; the raster's velocity sums keep
+field_reference.tolerance.
+
+x runs over the grid's ny = height / cell rows, y over one row's nx = width / cell columns; the flat cell index is
+row * nx + column (tests/test_gpu_large_grids.py)."""
+import time
+
+import numpy as np
+
+import close_pairs_reference as pairs_ref
+import clusters_reference as clusters_ref
+import encounters_reference as encounters_ref
+import field_reference as field_ref
+import neighbours_reference as neighbours_ref
+import rays_reference as rays_ref
+from rmf_crowdsim_amd import StubHighLevelPlan, _abi, scenes
+from select_reference import count, pred, select, selection
+from test_gpu_large_grids import BIG, LP, SCAN_TILE, WALK, _cluster, _grid, _line_crowd, tile_crowd
+from test_gpu_rays import ray_sets
+
+INF = float("inf")
+DT, STEPS = 0.1, 10
+CELLS = (0.6, 1.0, 2.5)  # the distances of the distance queries, in cells (and 0)
+
+
+class Scene:
+    """A grid description (the keywords of LocationHash2D) and the crowd on it: `parts` = (points, preferred velocity),
+    added in this order with local planner LP and an eyesight of one cell (the lattices: 0.7 m)."""
+
+    def __init__(self, name, grid, parts, eyesight=None, at_end=("row", "column", "cells")):
+        self.name, self.grid, self.parts = name, grid, parts
+        self.at_end = frozenset(at_end)  # which of the grid's last row, last column and last 32 x 32 cells the crowd stands in
+        self.cell = float(grid["cell_size"])
+        self.eyesight = self.cell if eyesight is None else eyesight
+        self.rows, self.cols = int(grid["height"] / self.cell), int(grid["width"] / self.cell)
+
+    def populate(self, sim, shift=0.0):
+        for pts, vel in self.parts:
+            sim.add_agents(np.asarray(pts) + shift, StubHighLevelPlan(vel), LP, self.eyesight)
+        return sim
+
+    def cells_of(self, rec):
+        """(row, column) of every record, by the division the index makes; records outside are not to be asked"""
+        ox, oy = self.grid["offset"]
+        return (np.floor((rec["x"] - ox) / self.cell).astype(np.int64), np.floor((rec["y"] - oy) / self.cell).astype(np.int64))
+
+    def flat_of(self, rec):
+        row, col = self.cells_of(rec)
+        return row * self.cols + col
+
+
+def _one_sided(name, nx, ny):
+    walkers, along_x = _line_crowd(nx, ny, 2100, 11)
+    fast, slow = ((WALK, 0.0), (0.8 * WALK, 0.0)) if along_x else ((0.0, WALK), (0.0, 0.8 * WALK))
+    # (the last cluster stands 2 to 14 cells before the high end of the long side: in the last 32 cells, not in the last one)
+    return Scene(name, _grid(nx, ny), [(walkers[0], fast), (walkers[1], slow)], at_end=("column" if along_x else "row", "cells"))
+
+
+def _lattice(origin):
+    """2,025 agents 0.5 m apart, each moved by up to 0.125 m: 22.5 m x 22.5 m from `origin`; nothing dyadic.  Everybody
+    walks along y, in files; every other file is slower and drifts 1.5 cm a second towards its neighbour, so that the model
+    turns it aside (walkers of one file keep their distance: crossing files meet within the model's collision distance
+    and the step gives NaN)."""
+    pts = scenes.jittered_lattice(2025, 0.5, origin, 0.25, 3, columns=45)
+    even = (np.arange(len(pts)) % 45) % 2 == 0
+    return [(pts[even], (0.0, WALK)), (pts[~even], (0.015, 0.8 * WALK))]
+
+
+def scene(name):
+    if name == "corridor":
+        return _one_sided(name, 1, 2_000_003)
+    if name == "strip":
+        return _one_sided(name, 2_000_003, 1)
+    if name == "tall5":
+        return _one_sided(name, 5, 200_000)
+    if name == "corridor2":  # (a mesh takes no tile thinner than two halo rings: its corridor is two cells wide)
+        return _one_sided(name, 2, 2_000_003)
+    if name == "strip2":
+        return _one_sided(name, 2_000_003, 2)
+    if name == "two-launch":
+        n, cell, off = 4097, 4.0, np.array([-30000.0, 45000.0])
+        walkers, standers = tile_crowd(n, n)
+        grid = dict(width=n * cell, height=n * cell, cell_size=cell, offset=tuple(off))
+        return Scene(name, grid, [(walkers[0] * cell + off, (0.0, WALK)), (walkers[1] * cell + off, (0.0, -WALK)),
+                                  (standers * cell + off, (0.0, 0.0))])
+    if name == "odd-cell":  # 176 columns x 111 rows; 123.4 / 0.7 = 176.29: the last 0.2 m of every row lie in no cell
+        grid = dict(width=123.4, height=77.7, cell_size=0.7, offset=(-1234.5, 6789.25))
+        # (the lattice stands in the middle of the grid: astride a mesh's cuts)
+        s = Scene(name, grid, _lattice((-1234.5 + 27.6, 6789.25 + 50.4)), eyesight=0.7, at_end=())
+        assert (s.rows, s.cols) == (111, 176)
+        return s
+    if name == "odd-far":  # half a cell more than 900 x 700 cells of 2.3 m: the quotient is not left to the rounding
+        grid = dict(width=900.5 * 2.3, height=700.5 * 2.3, cell_size=2.3, offset=(3.0e6, -2.0e6))
+        # (the lattice ends 5 m from the high corner)
+        s = Scene(name, grid, _lattice((3.0e6 + 700 * 2.3 - 27.5, -2.0e6 + 900 * 2.3 - 27.5)), eyesight=0.7, at_end=("cells",))
+        assert (s.rows, s.cols) == (700, 900)
+        return s
+    raise KeyError(name)
+
+
+def corner_scene(n):
+    """The 64 x 64 crowd of test_a_crowd_shifted_into_the_top_corner_of_a_grid_at_the_limit_steps_alike on an n x n grid
+    (populate it with shift = n - 64)."""
+    w = 64
+    p, a, b = _cluster(30.0, 30.0, w, w, 80, 56, (0.7, 1.0), 21, margin=2.0)
+    standers = np.concatenate([_cluster(0.5, 0.5, w, w, 4, 4, (0.6, 0.6), 22)[0],
+                               _cluster(w - 0.5, w - 0.5, w, w, 4, 4, (0.6, 0.6), 23)[0]])
+    return Scene(f"corner {n}", _grid(n, n), [(p[(a + b) % 2 == 0], (0.0, WALK)), (p[(a + b) % 2 == 1], (0.0, 0.8 * WALK)),
+                                               (standers, (0.0, 0.0))])
+
+
+def stepped(sc, make, shift=0.0, steps=STEPS):
+    """make(grid keywords) -> an engine or a mesh; populated and stepped"""
+    sim = sc.populate(make(sc.grid), shift)
+    for _ in range(steps):
+        sim.step(DT)
+    return sim
+
+
+# ---- floors: counted by the restatement alone, printed, asserted before the engine is asked --------------------------
+def pair_floor(sc, rec, least, least_across_tiles=None, cache=None):
+    """The pairs within one cell: at least `least`, `least_across_tiles` of them with their agents in different
+    1,024-cell scan tiles.  -> the restatement's pairs"""
+    want, _ = pairs_ref.pairs(rec, sc.grid, sc.cell, cache=cache)
+    tile_of = dict(zip(rec["id"].tolist(), (sc.flat_of(rec) // SCAN_TILE).tolist()))
+    across = sum(1 for p, q in want.tolist() if tile_of[p] != tile_of[q])
+    print(f"{sc.name}: restatement alone: {len(want)} pairs within one cell, {across} across a scan-tile boundary")
+    assert len(want) >= least
+    assert least_across_tiles is None or across >= least_across_tiles
+    return want
+
+
+# ---- the query families -----------------------------------------------------------------------------------------------
+def _sorted(rec):
+    return rec[np.argsort(rec["id"], kind="stable")]
+
+
+def _speeds(rec):
+    """(the speeds of the records with finite state, the middle between the slowest and the fastest)"""
+    speed = np.hypot(rec["vx"].astype(np.float64), rec["vy"].astype(np.float64))
+    speed = speed[np.isfinite(speed)]
+    return speed, float((speed.min() + speed.max()) / 2.0)
+
+
+def role_selections(rec):
+    """Two selections that need no ledger: the half of the crowd with the smaller x, and the slower walkers (or the
+    standers)."""
+    half = selection(_abi.CS_SEL_RECT, x0=-INF, y0=-INF, x1=float(np.nanmedian(rec["x"])), y1=INF)
+    slow = selection(_abi.CS_SEL_SPEED, speed_lo=0.0, speed_hi=_speeds(rec)[1])
+    return half, slow
+
+
+def ask_distance_queries(sim, sc, rec, name, cells=CELLS, roles=True, cache=None):
+    """cs_close_pairs, cs_agent_clusters and cs_agent_neighbours at 0 and at `cells` cells through each module's agree
+    (listing, count-only and capped forms), and once with two role selections.  -> {distance in cells: (pairs, d2)}"""
+    lhs = {} if cache is None else cache  # (the left-hand sides of this crowd, computed once for all its distances)
+    out = {}
+    for c in (0.0,) + tuple(cells):
+        d = c * sc.cell
+        want = pairs_ref.agree(sim, rec, sc.grid, d, name=f"{name}, pairs, {c} cells", cache=lhs)
+        clusters_ref.agree(sim, rec, sc.grid, d, name=f"{name}, clusters, {c} cells", cache=lhs)
+        neighbours_ref.agree(sim, rec, sc.grid, d, name=f"{name}, neighbours, {c} cells", cache=lhs, min_counts=(0, 2))
+        out[c] = want
+    assert len(out[0.0][0]) == 0 and len(out[1.0][0]) > 0
+    if roles:
+        half, slow = role_selections(rec)
+        d = sc.cell
+        both, _ = pairs_ref.agree(sim, rec, sc.grid, d, half, slow, name=f"{name}, pairs, two roles", cache=lhs)
+        assert 0 < len(both) < len(out[1.0][0])
+        neighbours_ref.agree(sim, rec, sc.grid, d, half, slow, name=f"{name}, neighbours, two roles", cache=lhs)
+        clusters_ref.agree(sim, rec, sc.grid, d, half, min_size=2, name=f"{name}, clusters of one role", cache=lhs)
+    return out
+
+
+def ask_encounters(sim, sc, rec, name, scale=1.0, range_=None, want=None):
+    """(distance, horizon, range) = (0.5 m, 3 s, 4 m) times the scale; range_: another range (a mesh sees as far as its halo)"""
+    rows = encounters_ref.agree(sim, rec, sc.grid, 0.5 * scale, 3.0, 4.0 * scale if range_ is None else range_,
+                                name=f"{name}, encounters", want=want)
+    assert len(rows) > 0 and (rows["t"] > 0.0).any()
+    return rows
+
+
+def ray_queries(sc, scale=1.0, longest=INF):
+    """(radius, reach) of the two ray queries, in metres"""
+    return [(0.2 * scale, min(30.0 * scale, longest)), (0.4 * scale, min(INF, longest))]
+
+
+def ask_rays(sim, sc, rec, name, scale=1.0, longest=INF, floors=True, want=None, rays=None):
+    """ray_sets(rec, grid, reach, beams=90) at both queries: the classes by the restatement alone (printed, then
+    asserted), then the engine.  -> [(rays, rows)]"""
+    out = []
+    for k, (radius, reach) in enumerate(ray_queries(sc, scale, longest)):
+        r = ray_sets(rec, sc.grid, reach, beams=90) if rays is None else rays[k]
+        stats = {}
+        w = rays_ref.cast(rec, sc.grid, r, radius, stats=stats) if want is None else want[k]
+        moving, still, miss = rays_ref.classes(w)
+        print(f"{name}, rays {(radius, reach)}: restatement alone: {moving} hits with t > 0, {still} with t == 0, {miss} "
+              f"misses, {stats.get('not_nearest')} winners that are not the candidate nearest the origin")
+        if floors:
+            assert moving >= 20 and still >= 20 and miss >= 20 and stats["not_nearest"] >= 5
+        rays_ref.agree(sim, rec, sc.grid, r, radius, name=f"{name}, rays {(radius, reach)}", want=w)
+        out.append((r, w))
+    return out
+
+
+def long_axis_rays(sc):
+    """16 rays from 5 m outside the low end of a one-sided grid along its long axis, spread over its short side,
+    t_max = +inf"""
+    gx0, gx1, gy0, gy1 = pairs_ref.rectangle(sc.grid)
+    k = np.arange(16) / 15.0  # (the first and the last run along the edges: nobody stands that close to them)
+    if sc.rows > sc.cols:
+        o, u = np.column_stack([np.full(16, gx0 - 5.0), gy0 + k * (gy1 - gy0)]), (1.0, 0.0)
+    else:
+        o, u = np.column_stack([gx0 + k * (gx1 - gx0), np.full(16, gy0 - 5.0)]), (0.0, 1.0)
+    return rays_ref.rays_array(o, np.repeat([u], 16, axis=0))
+
+
+def ask_long_axis_rays(sim, sc, rec, name, radius=0.2):
+    rays = long_axis_rays(sc)
+    want = rays_ref.cast(rec, sc.grid, rays, radius)
+    moving, still, miss = rays_ref.classes(want)
+    print(f"{name}, long-axis rays: restatement alone: {moving + still} hits, {miss} misses")
+    assert moving + still >= 8 and miss >= 2
+    t0 = time.perf_counter()
+    rays_ref.call(sim, rays[want["id"] == rays_ref.NO_HIT], radius)
+    dt = time.perf_counter() - t0
+    print(f"{name}: {miss} rays the whole length of {max(sc.rows, sc.cols):,} cells and back to the host in {dt * 1e3:.1f} ms")
+    rays_ref.agree(sim, rec, sc.grid, rays, radius, name=f"{name}, long-axis rays", want=want)
+    return want
+
+
+def region_selections(sc, rec):
+    """The cells of the last row, of the last column, the quadrant from the median agent to the high corner, a circle
+    round the agent in the first occupied cell, the faster walkers by a speed term."""
+    gx0, gx1, gy0, gy1 = pairs_ref.rectangle(sc.grid)
+    cell = sc.cell
+    first = rec[np.argmin(sc.flat_of(rec) + np.where(pairs_ref.takes_part(rec, sc.grid), 0, 2 ** 62))]
+    return [("the last row", selection(_abi.CS_SEL_RECT, x0=float(gx1 - cell), y0=float(gy0), x1=float(gx1), y1=float(gy1))),
+            ("the last column", selection(_abi.CS_SEL_RECT, x0=float(gx0), y0=float(gy1 - cell), x1=float(gx1), y1=float(gy1))),
+            ("the high quadrant", selection(_abi.CS_SEL_RECT, x0=float(np.nanmedian(rec["x"])), y0=float(np.nanmedian(rec["y"])),
+                                            x1=float(gx1), y1=float(gy1))),
+            ("round the first agent", selection(_abi.CS_SEL_CIRCLE, cx=float(first["x"]), cy=float(first["y"]), r=1.5 * cell)),
+            ("a speed", selection(_abi.CS_SEL_SPEED, speed_lo=_speeds(rec)[1], speed_hi=INF))]
+
+
+def ask_selections(sim, sc, rec, name, at_end=None):
+    """cs_select_agents (all ids, and under a cap) and cs_count_agents against select_reference.pred -> {name: ids}.
+    at_end: which of ("row", "column") must select somebody (None: where the scene's stepped crowd stands, sc.at_end; a
+    test that has written agents into the last cell or onto the edges passes both)."""
+    at_end = sc.at_end if at_end is None else frozenset(at_end)
+    sels = region_selections(sc, rec)
+    out = {}
+    for what, sel in sels:
+        want = rec["id"][pred(sel, rec, None, None, None)]
+        n, got = select(sim, sel)
+        print(f"{name}, select {what}: restatement {len(want)}, engine {n}")
+        assert n == len(want) and got.tolist() == want.tolist(), (name, what)
+        if len(want) > 3:
+            n, few = select(sim, sel, cap=len(want) // 2)
+            assert n == len(want) and few.tolist() == want[:len(want) // 2].tolist(), (name, what)
+        out[what] = want
+    rc, counts = count(sim, [s for _, s in sels])
+    assert rc == 0 and counts.tolist() == [len(out[what]) for what, _ in sels], name
+    assert len(out["the high quadrant"]) > 0 and len(out["round the first agent"]) > 0 and 0 < len(out["a speed"]) < len(rec)
+    for end in ("row", "column"):
+        if end in at_end:
+            assert len(out[f"the last {end}"]) > 0, (name, end)
+        else:
+            print(f"{name}: nobody is asked for in the last {end}: this crowd does not stand there")
+    return out
+
+
+def ask_removal(twin, sc, rec, name):
+    """remove_selected by the high quadrant on a twin: what is left is what the restatement leaves"""
+    what, sel = region_selections(sc, rec)[2]
+    gone = pred(sel, rec, None, None, None)
+    assert twin.read_agents().tobytes() == rec.tobytes(), name
+    ids = twin.remove_selected(rect=(sel.x0, sel.y0, sel.x1, sel.y1))
+    print(f"{name}, remove {what}: restatement {int(gone.sum())} of {len(rec)}, engine {len(ids)}")
+    assert 0 < gone.sum() < len(rec) and ids.tolist() == rec["id"][gone].tolist(), name
+    assert twin.read_agents().tobytes() == rec[~gone].tobytes(), name
+
+
+def ask_by_id(sim, rec, ids, name):
+    """read_agents_by_id gives the rows of read_agents(), in the order asked"""
+    at = {int(i): j for j, i in enumerate(rec["id"])}
+    assert sim.read_agents_by_id(ids).tobytes() == rec[[at[int(i)] for i in ids]].tobytes(), name
+
+
+class released:
+    """with released(engine, mesh, ...): every one gives its device memory back on the way out, also out of a failing
+    test (tiles of 2M cells and the 43 GB engine run in the same session as everything after them)."""
+
+    def __init__(self, *sims):
+        self.sims = sims
+
+    def __enter__(self):
+        return self.sims
+
+    def __exit__(self, *exc):
+        for s in self.sims:
+            s.close() if hasattr(s, "close") else s.__del__()
+        return False
+
+
+def rasters(sc, rec):
+    """(name, desc): the grid's last 32 x 32 cells (or its whole width), cell by cell; 16 x 16 and 130 x 130 bins of 1.3
+    cells from an origin 0.37 cell off the cell corners, over the cluster round the median agent.  The last is above
+    field_lds_limit() even without sums (67,600 B of counts)."""
+    ox, oy = sc.grid["offset"]
+    cell = sc.cell
+    nr, nc = min(32, sc.rows), min(32, sc.cols)
+    part = _sorted(rec[pairs_ref.takes_part(rec, sc.grid)])
+    row, col = sc.cells_of(part[len(part) // 2:len(part) // 2 + 1])
+    out = [("the last cells", field_ref.desc(ox + (sc.rows - nr) * cell, oy + (sc.cols - nc) * cell, cell, cell, nr, nc))]
+    for n in (16, 130):
+        out.append((f"{n} x {n} bins of 1.3 cells", field_ref.desc(
+            ox + (int(row[0]) + 0.37) * cell - 0.65 * n * cell, oy + (int(col[0]) + 0.37) * cell - 0.65 * n * cell,
+            1.3 * cell, 1.3 * cell, n, n)))
+    return out
+
+
+def ask_fields(sim, sc, rec, name, monkeypatch, at_end=None):
+    """Every raster as counts alone and with sums, in the form cs_agent_field picks and (CS_FIELD_LDS_BYTES=0) in the
+    global form.  at_end: with "cells" in it the raster of the last cells must hold somebody (None: sc.at_end)."""
+    at_end = sc.at_end if at_end is None else frozenset(at_end)
+    for what, d in rasters(sc, rec):
+        want = field_ref.raster(d, rec)
+        print(f"{name}, raster {what}: {int(want[0].sum())} agents in {int((want[0] > 0).sum())} of {want[0].size} bins")
+        assert want[0].sum() > 0 or (what == "the last cells" and "cells" not in at_end), (name, what)
+        for limit in (None, "0"):
+            if limit is None:
+                monkeypatch.delenv("CS_FIELD_LDS_BYTES", raising=False)
+            else:
+                monkeypatch.setenv("CS_FIELD_LDS_BYTES", limit)
+            for form in ("count", "both"):
+                rc, cnt, sums = field_ref.field(sim, d, None, want=form)
+                assert rc == 0, (name, what, field_ref.last_error(sim))
+                field_ref.check(f"{name}, {what}, {form}, LDS limit {limit}", cnt, sums, want)
+    monkeypatch.delenv("CS_FIELD_LDS_BYTES", raising=False)
+
+
+def ask_everything(sim, sc, rec, name, monkeypatch, scale=1.0, longest=INF, ray_floors=True, at_end=None):
+    ask_selections(sim, sc, rec, name, at_end)
+    ask_fields(sim, sc, rec, name, monkeypatch, at_end)
+    pairs = ask_distance_queries(sim, sc, rec, name)
+    rows = ask_encounters(sim, sc, rec, name, scale)
+    ask_rays(sim, sc, rec, name, scale, longest, floors=ray_floors)
+    assert sim.read_agents().tobytes() == rec.tobytes(), name  # (asking changes nothing)
+    return pairs, rows
+
+
+# ---- writes between steps ---------------------------------------------------------------------------------------------
+def boundary_tile(sc):
+    """k with the cells k * 1,024 - 1 and k * 1,024 in one row (where a row has more than one cell), a third of the way up
+    the grid"""
+    k = max(1, (sc.rows * sc.cols // SCAN_TILE) // 3)
+    while SCAN_TILE % sc.cols and (k * SCAN_TILE) % sc.cols == 0:  # (1 or 2 columns: the two cells are two rows)
+        k += 1
+    return k
+
+
+def move_into_cells(sc, rec, seed=5):
+    """Records of 48 agents with new positions: 16 in the grid's last cell, 16 in cell 0, 8 either side of the scan-tile
+    boundary boundary_tile() * 1,024.  In a cell they stand on a 4 x 4 (or 4 x 2) lattice 0.22 cell apart, 0.15 cell from
+    its low corner, so that no two are closer than the model's collision distance where the cell is 1 m."""
+    k = boundary_tile(sc)
+    part = _sorted(rec[pairs_ref.takes_part(rec, sc.grid)])
+    w = part[np.linspace(0, len(part) - 1, 48).astype(np.int64)].copy()
+    assert len(np.unique(w["id"])) == 48
+    ox, oy = sc.grid["offset"]
+    flats = [sc.rows * sc.cols - 1] * 16 + [0] * 16 + [k * SCAN_TILE - 1] * 8 + [k * SCAN_TILE] * 8
+    rng = np.random.default_rng(seed)
+    for j, flat in enumerate(flats):
+        row, col = divmod(flat, sc.cols)
+        slot = j % 16 if j < 32 else j % 8
+        fx = 0.15 + 0.22 * (slot % 4) + rng.uniform(0.0, 0.01)
+        fy = 0.15 + 0.22 * (slot // 4) + rng.uniform(0.0, 0.01)
+        w["x"][j] = ox + (row + fx) * sc.cell
+        w["y"][j] = oy + (col + fy) * sc.cell
+    w["vx"], w["vy"] = 0.0, 0.0  # (written with the position: nobody closes in on a neighbour 0.22 m away in the next step)
+    return w, k
+
+
+def check_moved(sim, sc, w, k, name):
+    """After write_agents(w): the agents are where they were written, by id and in read_agents(); the last cell and cell 0
+    hold at least 16 each; at least 10 pairs within one cell involve a moved agent (all by the restatement alone).
+    -> the records"""
+    rec = sim.read_agents()
+    back = sim.read_agents_by_id(w["id"])
+    at = {int(i): j for j, i in enumerate(rec["id"])}
+    assert back.tobytes() == rec[[at[int(i)] for i in w["id"]]].tobytes(), name
+    flat = sc.flat_of(rec)
+    held = [int((flat == f).sum()) for f in (sc.rows * sc.cols - 1, 0, k * SCAN_TILE - 1, k * SCAN_TILE)]
+    want, _ = pairs_ref.pairs(rec, sc.grid, sc.cell)
+    moved = int(np.isin(want, w["id"].astype(np.uint64)).any(axis=1).sum())
+    print(f"{name}: the last cell, cell 0 and the cells either side of tile boundary {k} hold {held}; {moved} of "
+          f"{len(want)} pairs within one cell involve a moved agent")
+    assert held[0] >= 16 and held[1] >= 16 and held[2] >= 8 and held[3] >= 8 and moved >= 10
+    assert np.array_equal(sc.flat_of(back), sc.flat_of(w)), name  # (each stands in the cell it was written into)
+    return rec
+
+
+def edge_agents(sc, rec, outsiders):
+    """Records of eight agents with new positions just inside every edge and corner of the participants' rectangle
+    (the low edges themselves, nextafter(high edge, -inf), the middle), of eight partners a third of a cell further in,
+    so that every edge agent is in a pair, and of `outsiders` more outside the rectangle that the index
+    still takes: one 0.3 cell below the low x edge (clamped into row 0), one 0.1 m beyond the last column where the grid's
+    width holds a partial cell (aliased into the next row; a mesh refuses that one).  -> (records, ids of the eight)"""
+    gx0, gx1, gy0, gy1 = pairs_ref.rectangle(sc.grid)
+    xs = (gx0, (gx0 + gx1) / 2.0 + 0.123, np.nextafter(gx1, -INF))
+    ys = (gy0, (gy0 + gy1) / 2.0 + 0.321, np.nextafter(gy1, -INF))
+    spots = [(x, y) for i, x in enumerate(xs) for j, y in enumerate(ys) if (i, j) != (1, 1)]
+    inward = (0.3 * sc.cell, 0.2 * sc.cell, -0.3 * sc.cell)  # a partner for each, 0.3 to 0.43 cell further in
+    spots += [(x + inward[i], y + inward[j]) for i, x in enumerate(xs) for j, y in enumerate(ys) if (i, j) != (1, 1)]
+    spots += [(gx0 - 0.3 * sc.cell, ys[1]), (xs[1], gy1 + 0.1)][:outsiders]
+    part = _sorted(rec[pairs_ref.takes_part(rec, sc.grid)])
+    w = part[np.linspace(5, len(part) - 6, len(spots)).astype(np.int64)].copy()
+    w["x"], w["y"] = [p[0] for p in spots], [p[1] for p in spots]
+    return w, w["id"][:8].copy()
+
+
+def check_edges(sc, rec, w, ids, outsiders):
+    """By the restatement alone: the edge agents and their partners are where they were written, to the f32 offset that
+    holds them; at least four of the eight take part (one whose offset rounds up to the cell size is reported ON the high
+    edge, outside) and are in a pair within one cell; the outsiders are held and take no part; the f64 rebuild matters."""
+    at = {int(i): j for j, i in enumerate(rec["id"])}
+    rows = rec[[at[int(i)] for i in w["id"]]]  # (a cell and an f32 offset hold them: not the written bits)
+    # an f32 offset of at most one cell: 2^-24 of it, and the rounding of the f64 sum; an outsider's offset is measured from
+    # the cell it is clamped or aliased into and may be as long as the grid
+    tol = np.where(np.arange(len(w)) < 16, 1e-6 * sc.cell, 2.0 ** -23 * max(sc.grid["width"], sc.grid["height"]))
+    assert (np.abs(rows["x"] - w["x"]) <= tol).all() and (np.abs(rows["y"] - w["y"]) <= tol).all()
+    part = pairs_ref.takes_part(rows, sc.grid)
+    want, _ = pairs_ref.pairs(rec, sc.grid, sc.cell)
+    paired = int(np.isin(ids.astype(np.uint64), want).sum())
+    print(f"{sc.name}: {int(part[:8].sum())} of the 8 edge agents take part, {paired} of them in a pair within one cell; "
+          f"{int(part[16:].sum())} of {outsiders} outsiders take part")
+    assert part[:8].sum() >= 4 and paired >= 4 and part[8:16].all() and not part[16:].any() and len(part) == 16 + outsiders
+    ox, oy = sc.grid["offset"]
+    took = rec[pairs_ref.takes_part(rec, sc.grid)]
+    through_f32 = sum(int((took[c] != o + (took[c] - o).astype(np.float32).astype(np.float64)).sum())
+                      for c, o in (("x", ox), ("y", oy)))
+    print(f"{sc.name}: {through_f32} coordinates of participants differ from offset + (float32)(coordinate - offset)")
+    assert through_f32 >= 1
+
+
+# ---- meshes -----------------------------------------------------------------------------------------------------------
+def cuts_of(rects):
+    """(rows, columns) at which a tile of a mesh begins, other than 0, from its tile_rects()"""
+    r = np.asarray(rects, dtype=np.int64)
+    return sorted(set(r[:, 0].tolist()) - {0}), sorted(set(r[:, 2].tolist()) - {0})
+
+
+def astride_cuts(sc, rec, rects):
+    """Records of four agents with new positions astride every cut: 0.3 and 0.1 cell either side of it, in the middle of
+    the grid's other axis"""
+    cut_rows, cut_cols = cuts_of(rects)
+    ox, oy = sc.grid["offset"]
+    spots = []
+    for j, f in enumerate((-0.3, -0.1, 0.1, 0.3)):
+        spots += [(ox + (c + f) * sc.cell, oy + (sc.cols // 2 + 0.4 + 0.05 * j) * sc.cell) for c in cut_rows]
+        spots += [(ox + (sc.rows // 2 + 0.4 + 0.05 * j) * sc.cell, oy + (c + f) * sc.cell) for c in cut_cols]
+    part = _sorted(rec[pairs_ref.takes_part(rec, sc.grid)])
+    w = part[np.linspace(3, len(part) - 4, len(spots)).astype(np.int64)].copy()
+    w["x"], w["y"] = [p[0] for p in spots], [p[1] for p in spots]
+    return w
+
+
+def cut_floor(sc, rec, rects, distance):
+    """By the restatement alone: pairs within `distance` whose agents stand on either side of a cut, every cut"""
+    want, _ = pairs_ref.pairs(rec, sc.grid, distance)
+    row, col = sc.cells_of(rec)
+    at = {int(i): j for j, i in enumerate(rec["id"])}
+    p, q = [at[v] for v in want[:, 0].tolist()], [at[v] for v in want[:, 1].tolist()]
+    cut_rows, cut_cols = cuts_of(rects)
+    across = [int(((row[p] < c) != (row[q] < c)).sum()) for c in cut_rows] + \
+             [int(((col[p] < c) != (col[q] < c)).sum()) for c in cut_cols]
+    print(f"{sc.name}: cuts at rows {cut_rows} and columns {cut_cols}: of {len(want)} pairs within {distance} m, "
+          f"{across} across them")
+    assert len(across) > 0 and all(n > 0 for n in across)
+
