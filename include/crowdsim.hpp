@@ -582,6 +582,29 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     if (hits == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
     return hits;
   }
+  // Who comes within `distance` of each timed leg first if the crowd keeps walking as it does now (cs_leg_conflicts,
+  // include/crowdstep_state.h "Paths against the moving crowd between steps"): a leg is a probe at (x0, y0) at t0 moving
+  // with (vx, vy) until t1, seconds from now ((0, 0): a wait); row k of the answer is the first agent slower than
+  // speed_max to come within the distance of leg k and the seconds s after t0 at which it does, bit for bit;
+  // {CS_NO_HIT, +inf} for a free leg.  `targets`: who can conflict (null: everyone).
+  std::vector<cs_leg_hit> leg_conflicts(const cs_leg* legs, std::size_t n, double distance, double speed_max,
+                                        const cs_selection* targets = nullptr) {
+    std::vector<cs_leg_hit> out(n);
+    const std::size_t hits = cs_leg_conflicts(engine_, legs, n, distance, speed_max, targets, out.data());
+    if (hits == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return out;
+  }
+  std::vector<cs_leg_hit> leg_conflicts(const std::vector<cs_leg>& legs, double distance, double speed_max,
+                                        const cs_selection* targets = nullptr) {
+    return leg_conflicts(legs.data(), legs.size(), distance, speed_max, targets);
+  }
+  // the number of legs of leg_conflicts(...) with a conflict; no rows are written
+  std::size_t count_leg_conflicts(const std::vector<cs_leg>& legs, double distance, double speed_max,
+                                  const cs_selection* targets = nullptr) {
+    const std::size_t hits = cs_leg_conflicts(engine_, legs.data(), legs.size(), distance, speed_max, targets, nullptr);
+    if (hits == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return hits;
+  }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
     std::vector<AgentId> ids(cs_agent_count(engine_));
@@ -955,6 +978,29 @@ class TiledSimulation {
   // the number of rays of cast_rays(...) that hit somebody; no rows are written
   std::size_t count_ray_hits(const std::vector<cs_ray>& rays, double radius, const cs_selection* targets = nullptr) {
     const std::size_t hits = cs_mesh_cast_rays(mesh_, rays.data(), rays.size(), radius, targets, nullptr);
+    if (hits == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return hits;
+  }
+  // Who comes within `distance` of each timed leg first if the crowd keeps walking as it does now (cs_mesh_leg_conflicts,
+  // include/crowdstep_state.h "Paths against the moving crowd between steps"): a leg is a probe at (x0, y0) at t0 moving
+  // with (vx, vy) until t1, seconds from now ((0, 0): a wait); row k of the answer is the first agent slower than
+  // speed_max to come within the distance of leg k and the seconds s after t0 at which it does, bit for bit;
+  // {CS_NO_HIT, +inf} for a free leg.  `targets`: who can conflict (null: everyone).
+  std::vector<cs_leg_hit> leg_conflicts(const cs_leg* legs, std::size_t n, double distance, double speed_max,
+                                        const cs_selection* targets = nullptr) {
+    std::vector<cs_leg_hit> out(n);
+    const std::size_t hits = cs_mesh_leg_conflicts(mesh_, legs, n, distance, speed_max, targets, out.data());
+    if (hits == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return out;
+  }
+  std::vector<cs_leg_hit> leg_conflicts(const std::vector<cs_leg>& legs, double distance, double speed_max,
+                                        const cs_selection* targets = nullptr) {
+    return leg_conflicts(legs.data(), legs.size(), distance, speed_max, targets);
+  }
+  // the number of legs of leg_conflicts(...) with a conflict; no rows are written
+  std::size_t count_leg_conflicts(const std::vector<cs_leg>& legs, double distance, double speed_max,
+                                  const cs_selection* targets = nullptr) {
+    const std::size_t hits = cs_mesh_leg_conflicts(mesh_, legs.data(), legs.size(), distance, speed_max, targets, nullptr);
     if (hits == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
     return hits;
   }

@@ -523,6 +523,71 @@ size_t cs_cast_rays(cs_engine*, const cs_ray* rays, size_t n, double radius, con
 size_t cs_mesh_cast_rays(cs_mesh*, const cs_ray* rays, size_t n, double radius, const cs_selection* targets,
                          cs_ray_hit* out);
 
+/* Paths against the moving crowd between steps.  A route planner holds a TIMED path ("from A to B between 0 s and 2 s,
+ * wait until 3.5 s, then to C by 6 s") and asks whether anyone comes within `distance` of it if the crowd keeps walking
+ * as it does now, and if so who comes first, when and where.  A LEG is one piece of such a path: a probe point that is at
+ * (x0, y0) at time t0 and moves with velocity (vx, vy) until t1, times in seconds from now; v = (0, 0) is a wait (can
+ * this door close during the next 2 s).  A path is any number of legs and each leg is answered on its own.
+ *
+ * An agent is the record cs_read_agents returns for it: x, y in f64 and vx, vy the f32 velocity widened to f64, kept
+ * constant.  PARTICIPANTS are the pairs' participants: the agents whose reported position is finite and inside the
+ * grid's own rectangle (on a tile or a mesh: the global one; on a tile engine with ghosts only owned agents).  `targets`
+ * (NULL: everyone) restricts who can conflict; everybody else is transparent.
+ *
+ * THE RULE, for leg (x0, y0, vx, vy, t0, t1, ignore) and participant q != ignore, with D2 = distance * distance and
+ * T = t1 - t0, every operation one f64 operation rounded once (no contraction, no reciprocal, no f32 pre-reject, the
+ * correctly rounded division and square root):
+ *     ss = vx_q*vx_q + vy_q*vy_q;       SLOW ENOUGH iff ss < speed_max*speed_max   (else q is not considered; a NaN is not)
+ *     px = x_q + vx_q*t0;  py = y_q + vy_q*t0                                     (where q is when the leg begins)
+ *     rx = px - x0;  ry = py - y0;  wx = vx_q - vx;  wy = vy_q - vy
+ *     d2 = rx*rx + ry*ry
+ *     if d2 < D2:              s = +0.0                  (already within the distance when the leg begins)
+ *     else:
+ *       a  = rx*wx + ry*wy;    miss if !(a < 0)          (not approaching; equal velocities; a NaN)
+ *       ww = wx*wx + wy*wy
+ *       cr = rx*wy - ry*wx
+ *       h2 = D2*ww - cr*cr;    miss if !(h2 > 0)         (grazing is a miss)
+ *       s  = (-a - sqrt(h2)) / ww;   if s < 0: s = +0.0  (rounding only)
+ *     CONFLICT iff s < T
+ * The answer of a leg is the lexicographic minimum of (s, id) over its conflicts (of two agents that arrive at the same
+ * s the smaller id), or {CS_NO_HIT, +inf}.  It depends neither on slots nor on tiles.  The time of the conflict is
+ * t0 + s and the probe is then at (x0 + vx*s, y0 + vy*s).  T == 0 and distance == 0 give nothing; distance = +inf and
+ * speed_max = +inf are allowed everywhere, the grid being finite.
+ *
+ * speed_max is part of the definition because it is what makes a bounded search sound: an agent slower than speed_max
+ * that conflicts during the leg stands NOW within distance + speed_max * t1 of the segment the probe sweeps, and the
+ * device looks no further.  A host that wants nobody left out passes a bound at or above its planners' top speed;
+ * cs_count_agents with CS_SEL_SPEED tells it how many agents exceed a bound.
+ *
+ * Refused (SIZE_MAX, nothing written, the engine or mesh still usable; the text names the first bad leg): n >
+ * CS_LEGS_MAX, legs == NULL with n > 0, a NaN or negative distance or speed_max, a leg with a non-finite x0, y0, vx, vy,
+ * t0 or t1, with t0 < 0 or with t1 < t0, a selection cs_select_agents refuses.  Queued steps complete first and an Err of
+ * one of them is the call's; no events, the last step report is left alone, nothing is renumbered, and a twin that never
+ * asks stays byte-equal. */
+#define CS_LEGS_MAX (1u << 20)          /* legs of one call */
+typedef struct cs_leg {                 /* 56 bytes */
+  double x0, y0;        /* where the probe is at t0, world coordinates, finite                 */
+  double vx, vy;        /* its velocity during the leg; finite; (0, 0) is a wait               */
+  double t0, t1;        /* 0 <= t0 <= t1, both finite, seconds from now                        */
+  uint64_t ignore;      /* an agent id the leg passes through (the robot itself);
+                           CS_NO_HIT: nobody; an id that is not alive: nobody                  */
+} cs_leg;
+typedef struct cs_leg_hit {             /* 16 bytes */
+  uint64_t id;          /* the first agent to come within `distance`; CS_NO_HIT: none          */
+  double   s;           /* seconds after t0 at which it does, bit for bit by the rule; +inf when none */
+} cs_leg_hit;
+/* Checks n legs; row k of `out` (n rows; may be NULL) is the answer of leg k.  Returns the number of legs with a
+ * conflict (n == 0: 0), SIZE_MAX on error. */
+size_t cs_leg_conflicts(cs_engine*, const cs_leg* legs, size_t n, double distance, double speed_max,
+                        const cs_selection* targets, cs_leg_hit* out /* n rows, row k for leg k; may be NULL */);
+/* The same on a mesh.  Collective: every rank passes the same legs and gets the single engine's answer, byte for byte.
+ * No halo exchange is made, there are no band records, and distance, speed_max and t1 have no limit: every tile runs ALL
+ * legs against the agents it owns and one gather moves n 16-byte rows per rank; every rank takes the lexicographic
+ * minimum of (s, id) per leg.  The number of collectives depends neither on the crowd nor on the answer.  A tile that
+ * fails makes every rank return SIZE_MAX.  The step's exchange state is not touched. */
+size_t cs_mesh_leg_conflicts(cs_mesh*, const cs_leg* legs, size_t n, double distance, double speed_max,
+                             const cs_selection* targets, cs_leg_hit* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -260,6 +260,7 @@ CS_PAIRS_MAX = 1 << 26
 CS_NO_NEIGHBOUR = 0xFFFFFFFFFFFFFFFF
 CS_NO_HIT = 0xFFFFFFFFFFFFFFFF
 CS_RAYS_MAX = 1 << 20
+CS_LEGS_MAX = 1 << 20
 
 
 class Selection(C.Structure):
@@ -309,6 +310,18 @@ class RayHit(C.Structure):
     _fields_ = [("id", C.c_uint64), ("t", C.c_double)]
 
 
+class Leg(C.Structure):
+    """cs_leg: one leg of a timed path for cs_leg_conflicts; the probe at t0 + s is (x0, y0) + v * s
+    (include/crowdstep_state.h)"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("vx", C.c_double), ("vy", C.c_double), ("t0", C.c_double),
+                ("t1", C.c_double), ("ignore", C.c_uint64)]
+
+
+class LegHit(C.Structure):
+    """cs_leg_hit: the answer of one leg; id == CS_NO_HIT and s == +inf when nobody conflicts"""
+    _fields_ = [("id", C.c_uint64), ("s", C.c_double)]
+
+
 _PAIRS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.POINTER(IdPair), C.POINTER(C.c_double),
                C.c_size_t]
 _CLUSTERS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -318,6 +331,7 @@ _NEIGHBOURS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Sele
 _ENCOUNTERS_ARGS = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.POINTER(Selection), C.POINTER(Selection),
                     C.POINTER(Encounter), C.c_size_t]
 _RAYS_ARGS = [C.c_void_p, C.POINTER(Ray), C.c_size_t, C.c_double, C.POINTER(Selection), C.POINTER(RayHit)]
+_LEGS_ARGS = [C.c_void_p, C.POINTER(Leg), C.c_size_t, C.c_double, C.c_double, C.POINTER(Selection), C.POINTER(LegHit)]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -354,6 +368,8 @@ STATE_SYMBOLS = {
     "cs_mesh_encounters": (C.c_size_t, list(_ENCOUNTERS_ARGS)),
     "cs_cast_rays": (C.c_size_t, list(_RAYS_ARGS)),
     "cs_mesh_cast_rays": (C.c_size_t, list(_RAYS_ARGS)),
+    "cs_leg_conflicts": (C.c_size_t, list(_LEGS_ARGS)),
+    "cs_mesh_leg_conflicts": (C.c_size_t, list(_LEGS_ARGS)),
 }
 
 

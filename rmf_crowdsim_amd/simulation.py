@@ -804,6 +804,83 @@ def cast_rays_of(fn, handle, handle_of, err, rays, radius, targets, want_rows):
     return int(got), (rows[:n].copy() if want_rows else None)
 
 
+LEG_DTYPE = np.dtype([("x0", np.float64), ("y0", np.float64), ("vx", np.float64), ("vy", np.float64),
+                      ("t0", np.float64), ("t1", np.float64), ("ignore", np.uint64)])
+LEG_HIT_DTYPE = np.dtype([("id", np.uint64), ("s", np.float64)])
+assert LEG_DTYPE.itemsize == C.sizeof(_abi.Leg) == 56 and LEG_HIT_DTYPE.itemsize == C.sizeof(_abi.LegHit) == 16
+
+
+def legs_array(starts, velocities, t0, t1, ignore=None):
+    """The LEG_DTYPE array of n legs: starts and velocities are (n, 2), or one pair for all legs; t0, t1 and ignore one
+    value for all or one per leg (ignore None: nobody)."""
+    starts = np.asarray(starts, dtype=np.float64).reshape(-1, 2)
+    velocities = np.asarray(velocities, dtype=np.float64).reshape(-1, 2)
+    n = np.broadcast_shapes((len(starts),), (len(velocities),), np.shape(t0), np.shape(t1),
+                            () if ignore is None else np.shape(ignore))
+    if len(n) != 1:
+        raise ValueError("leg_conflicts: t0, t1 and ignore are scalars or one value per leg")
+    legs = np.zeros(n[0], dtype=LEG_DTYPE)
+    legs["x0"], legs["y0"] = starts[:, 0], starts[:, 1]
+    legs["vx"], legs["vy"] = velocities[:, 0], velocities[:, 1]
+    legs["t0"] = np.asarray(t0, dtype=np.float64)
+    legs["t1"] = np.asarray(t1, dtype=np.float64)
+    legs["ignore"] = _abi.CS_NO_HIT if ignore is None else np.asarray(ignore, dtype=np.uint64)
+    return legs
+
+
+def _path_legs(waypoints, times, ignore=None):
+    """The legs of one timed polyline of k + 1 points: leg i runs from point i at times[i] to point i + 1 at
+    times[i + 1] with velocity (p[i + 1] - p[i]) / (times[i + 1] - times[i]); a zero-duration leg is dropped, equal points
+    over a positive duration are a wait."""
+    p = np.asarray(waypoints, dtype=np.float64).reshape(-1, 2)
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    if len(p) != len(t) or len(t) < 1:
+        raise ValueError("path_conflict: as many times as waypoints, and at least one")
+    if not (np.isfinite(p).all() and np.isfinite(t).all() and t[0] >= 0.0 and (np.diff(t) >= 0.0).all()):
+        raise ValueError("path_conflict: finite waypoints and finite non-decreasing times, the first >= 0")
+    keep = np.diff(t) > 0.0
+    lo, hi = t[:-1][keep], t[1:][keep]
+    return legs_array(p[:-1][keep], (p[1:][keep] - p[:-1][keep]) / (hi - lo)[:, None], lo, hi, ignore)
+
+
+def paths_legs(paths):
+    """Many timed paths as one array of legs: paths is a list of (waypoints, times) as for path_conflict.  Returns (legs,
+    path_of_leg): the LEG_DTYPE legs of all paths in order (ignore: nobody; set legs["ignore"] as needed) and for each leg
+    the index of its path, so that one leg_conflicts call answers all paths and numpy reduces its rows."""
+    legs = [_path_legs(w, t) for w, t in paths]
+    owner = [np.full(len(l), k, dtype=np.int64) for k, l in enumerate(legs)]
+    if not legs:
+        return np.zeros(0, dtype=LEG_DTYPE), np.zeros(0, dtype=np.int64)
+    return np.concatenate(legs), np.concatenate(owner)
+
+
+def leg_conflicts_of(fn, handle, handle_of, err, legs, distance, speed_max, targets, want_rows):
+    """leg_conflicts and count_leg_conflicts of Simulation and NativeTileMesh -> (the number of legs with a conflict, the
+    LEG_HIT_DTYPE rows or None)"""
+    sel = None if targets is None else selection_struct(targets, handle_of)
+    legs = np.ascontiguousarray(legs, dtype=LEG_DTYPE)
+    n = len(legs)
+    rows = np.zeros(max(n, 1), dtype=LEG_HIT_DTYPE) if want_rows else None
+    got = fn(handle, legs.ctypes.data_as(C.POINTER(_abi.Leg)) if n else None, n, float(distance), float(speed_max),
+             C.byref(sel) if sel is not None else None,
+             rows.ctypes.data_as(C.POINTER(_abi.LegHit)) if want_rows else None)
+    if got == _SIZE_MAX:
+        raise err()
+    return int(got), (rows[:n].copy() if want_rows else None)
+
+
+def path_conflict_of(leg_conflicts, waypoints, times, distance, speed_max, ignore, targets):
+    """path_conflict of Simulation and NativeTileMesh over their leg_conflicts"""
+    legs = _path_legs(waypoints, times, ignore)
+    rows = leg_conflicts(legs, distance, speed_max, targets=targets)
+    hit = np.nonzero(rows["id"] != np.uint64(_abi.CS_NO_HIT))[0]
+    if not len(hit):
+        return None
+    k = int(hit[0])
+    l, s = legs[k], float(rows["s"][k])
+    return int(rows["id"][k]), float(l["t0"]) + s, k, (float(l["x0"]) + float(l["vx"]) * s, float(l["y0"]) + float(l["vy"]) * s)
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -1237,6 +1314,34 @@ class Simulation:
         fn = state_fn(self._lib, self.backend, "cs_cast_rays", "cast_rays")
         return cast_rays_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err,
                             rays_array(origins, directions, t_max, ignore), radius, targets, False)[0]
+
+    def leg_conflicts(self, legs, distance, speed_max, *, targets=None):
+        """Who comes within `distance` of each timed leg first if the crowd keeps walking as it does now, on the device
+        (cs_leg_conflicts).  legs: a LEG_DTYPE array (legs_array, paths_legs): a probe at (x0, y0) at time t0 moving with
+        (vx, vy) until t1, seconds from now; (0, 0) is a wait; ignore is an agent id the leg passes through (the robot
+        itself).  Agents at or above speed_max are not considered: the bound is what lets the device look no further than
+        distance + speed_max * t1 from the leg, so pass the planners' top speed or more (inf: everyone, the whole grid is
+        walked).  targets: who can conflict (a selection as for select_agents; None: everyone).  Returns a structured
+        array (id, s), row k for leg k: the first agent and the seconds after t0 at which it comes within the distance,
+        bit for bit the f64 rule of include/crowdstep_state.h, of equal s the smaller id; (_abi.CS_NO_HIT, inf) for a
+        free leg.  Changes nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_leg_conflicts", "leg_conflicts")
+        return leg_conflicts_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, legs, distance,
+                                speed_max, targets, True)[1]
+
+    def count_leg_conflicts(self, legs, distance, speed_max, *, targets=None):
+        """The number of legs of leg_conflicts(...) with a conflict; no rows are written."""
+        fn = state_fn(self._lib, self.backend, "cs_leg_conflicts", "leg_conflicts")
+        return leg_conflicts_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, legs, distance,
+                                speed_max, targets, False)[0]
+
+    def path_conflict(self, waypoints, times, distance, speed_max, *, ignore=None, targets=None):
+        """One timed polyline against the moving crowd: waypoints (k + 1, 2) reached at the non-decreasing finite `times`
+        (the first >= 0), each piece a leg of leg_conflicts (a zero-duration piece is dropped, equal points over a positive
+        duration are a wait).  Returns None, or (id, t, leg_index, (x, y)) of the first leg in path order that has a
+        conflict: who, the time t = t0 + s from now, the leg (counted without the dropped ones) and where the probe is
+        then."""
+        return path_conflict_of(self.leg_conflicts, waypoints, times, distance, speed_max, ignore, targets)
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

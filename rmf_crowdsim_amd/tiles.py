@@ -823,6 +823,27 @@ class NativeTileMesh:
         return cast_rays_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err,
                             rays_array(origins, directions, t_max, ignore), radius, targets, False)[0]
 
+    def leg_conflicts(self, legs, distance, speed_max, *, targets=None):
+        """Simulation.leg_conflicts on the mesh (cs_mesh_leg_conflicts): the single engine's answer, byte for byte
+        (collective in the distributed form).  Every tile runs all legs against the agents it owns and the rows are merged
+        by the minimum of (s, id); distance, speed_max and t1 have no limit and no halo exchange is made."""
+        from .simulation import leg_conflicts_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_leg_conflicts", "leg_conflicts")
+        return leg_conflicts_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, legs, distance, speed_max,
+                                targets, True)[1]
+
+    def count_leg_conflicts(self, legs, distance, speed_max, *, targets=None):
+        """Simulation.count_leg_conflicts on the mesh (collective in the distributed form)."""
+        from .simulation import leg_conflicts_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_leg_conflicts", "leg_conflicts")
+        return leg_conflicts_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, legs, distance, speed_max,
+                                targets, False)[0]
+
+    def path_conflict(self, waypoints, times, distance, speed_max, *, ignore=None, targets=None):
+        """Simulation.path_conflict on the mesh (one leg_conflicts call; collective in the distributed form)."""
+        from .simulation import path_conflict_of
+        return path_conflict_of(self.leg_conflicts, waypoints, times, distance, speed_max, ignore, targets)
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
