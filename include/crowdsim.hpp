@@ -605,6 +605,33 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     if (hits == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
     return hits;
   }
+  // Everybody who comes within `distance` of each timed leg, and when (cs_leg_intervals, include/crowdstep_state.h "Every
+  // agent that enters a leg"): one row per (leg, agent) that conflicts by the rule of leg_conflicts, ascending by
+  // (leg, id): the agent is within the distance from t0 + s_in to t0 + s_out, s_out at most t1 - t0, bit for bit.
+  // `limit`: at most that many rows (the first ones); a listing of more than CS_PAIRS_MAX rows throws,
+  // count_leg_intervals has no limit.
+  std::vector<cs_leg_interval> leg_intervals(const std::vector<cs_leg>& legs, double distance, double speed_max,
+                                             const cs_selection* targets = nullptr, std::size_t limit = SIZE_MAX) {
+    std::vector<cs_leg_interval> out;
+    const std::size_t count = cs_leg_intervals(engine_, legs.data(), legs.size(), distance, speed_max, targets, nullptr, nullptr, 0);
+    if (count == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    std::size_t cap = std::min(count, limit);
+    if (!cap) return out;
+    if (count > CS_PAIRS_MAX) cap = 1;  // (refused by the library, with its message: no room is made for it here)
+    out.resize(cap);
+    const std::size_t n = cs_leg_intervals(engine_, legs.data(), legs.size(), distance, speed_max, targets, nullptr, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  // the number of rows of leg_intervals(...) per leg, from one pass that lists nothing, exact whatever its size
+  std::vector<uint64_t> count_leg_intervals(const std::vector<cs_leg>& legs, double distance, double speed_max,
+                                            const cs_selection* targets = nullptr) {
+    std::vector<uint64_t> counts(legs.size());
+    const std::size_t n = cs_leg_intervals(engine_, legs.data(), legs.size(), distance, speed_max, targets, counts.data(), nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return counts;
+  }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
     std::vector<AgentId> ids(cs_agent_count(engine_));
@@ -1003,6 +1030,33 @@ class TiledSimulation {
     const std::size_t hits = cs_mesh_leg_conflicts(mesh_, legs.data(), legs.size(), distance, speed_max, targets, nullptr);
     if (hits == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
     return hits;
+  }
+  // Everybody who comes within `distance` of each timed leg, and when (cs_mesh_leg_intervals, include/crowdstep_state.h "Every
+  // agent that enters a leg"): one row per (leg, agent) that conflicts by the rule of leg_conflicts, ascending by
+  // (leg, id): the agent is within the distance from t0 + s_in to t0 + s_out, s_out at most t1 - t0, bit for bit.
+  // `limit`: at most that many rows (the first ones); a listing of more than CS_PAIRS_MAX rows throws,
+  // count_leg_intervals has no limit.
+  std::vector<cs_leg_interval> leg_intervals(const std::vector<cs_leg>& legs, double distance, double speed_max,
+                                             const cs_selection* targets = nullptr, std::size_t limit = SIZE_MAX) {
+    std::vector<cs_leg_interval> out;
+    const std::size_t count = cs_mesh_leg_intervals(mesh_, legs.data(), legs.size(), distance, speed_max, targets, nullptr, nullptr, 0);
+    if (count == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    std::size_t cap = std::min(count, limit);
+    if (!cap) return out;
+    if (count > CS_PAIRS_MAX) cap = 1;  // (refused by the library, with its message: no room is made for it here)
+    out.resize(cap);
+    const std::size_t n = cs_mesh_leg_intervals(mesh_, legs.data(), legs.size(), distance, speed_max, targets, nullptr, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  // the number of rows of leg_intervals(...) per leg, from one pass that lists nothing, exact whatever its size
+  std::vector<uint64_t> count_leg_intervals(const std::vector<cs_leg>& legs, double distance, double speed_max,
+                                            const cs_selection* targets = nullptr) {
+    std::vector<uint64_t> counts(legs.size());
+    const std::size_t n = cs_mesh_leg_intervals(mesh_, legs.data(), legs.size(), distance, speed_max, targets, counts.data(), nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return counts;
   }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {

@@ -588,6 +588,52 @@ size_t cs_leg_conflicts(cs_engine*, const cs_leg* legs, size_t n, double distanc
 size_t cs_mesh_leg_conflicts(cs_mesh*, const cs_leg* legs, size_t n, double distance, double speed_max,
                              const cs_selection* targets, cs_leg_hit* out);
 
+/* Every agent that enters a leg, with the time it enters and the time it leaves.  cs_leg_conflicts says who comes within
+ * `distance` of a leg FIRST; a planner that has to wait (a safe-interval planner asking when a vertex or a lane of its
+ * graph is occupied during a horizon, a door interlock asking when the threshold is free for 2 s in a row) needs every
+ * interval during which somebody is within the distance.  cs_leg_intervals lists them: one row per (leg, agent) that
+ * conflicts.  Two points that move uniformly are apart by a convex quadratic of time, so a pair has at most one interval.
+ *
+ * THE RULE.  The legs, the participants, `targets`, `ignore`, the speed test and s_in are those of cs_leg_conflicts, word
+ * for word: (leg k, agent q) is a row exactly when q is a conflict of leg k there, and s_in is that rule's s, the same
+ * bits.  s_out is new; every operation is again one f64 operation rounded once, and a, ww, cr and h2 are computed also for
+ * a candidate that is inside at the start:
+ *     (ss, px, py, rx, ry, wx, wy, d2 as there)
+ *     a = rx*wx + ry*wy;  ww = wx*wx + wy*wy;  cr = rx*wy - ry*wx;  h2 = D2*ww - cr*cr
+ *     s_in:   +0.0 if d2 < D2;  else miss if !(a < 0), miss if !(h2 > 0), s_in = (-a - sqrt(h2)) / ww, +0.0 if s_in < 0
+ *     ROW iff s_in < T
+ *     s_out:  if !(h2 > 0):   T if ww == 0 (the same velocity, inside: it never leaves), else s_in (rounding only)
+ *             else:           e = (-a + sqrt(h2)) / ww;  if !(e > s_in) e = s_in;  if !(e < T) e = T;  s_out = e
+ * so 0 <= s_in <= s_out <= T; the agent is within the distance from t0 + s_in to t0 + s_out, and s_out == T says that it
+ * is still there when the leg ends.  distance = +inf gives [0, T] for every slow participant (inf * ww is inf for ww > 0
+ * and inf * 0 is a NaN, which takes the ww == 0 branch); T == 0 and distance == 0 give no rows.
+ *
+ * THE ANSWER.  Every row once, ascending by (leg, id).  The call returns the full count and writes the first
+ * min(count, cap) rows, nothing beyond them; out_counts[k], if given, is the full number of rows of leg k whatever cap is.
+ * out == NULL or cap == 0 asks for the counts only: one pass that makes no row, with a 64-bit total on the device, and no
+ * limit.  With cap > 0 a count above CS_PAIRS_MAX is refused (SIZE_MAX, "too many intervals to list", the engine usable).
+ * Every other refusal is that of cs_leg_conflicts (the text says leg_intervals and names the first bad leg); after a
+ * refusal nothing is written, out_counts included.  n == 0 returns 0.  Queued steps complete first and an Err of one of
+ * them is the call's; no events, the last step report is left alone, nothing is renumbered, and a twin that never asks
+ * stays byte-equal. */
+typedef struct cs_leg_interval {        /* 32 bytes */
+  uint64_t leg;         /* index of the leg in the call                                        */
+  uint64_t id;          /* the agent (the external id under CS_CFG_WIDE_IDS)                   */
+  double   s_in;        /* seconds after t0 at which it comes within `distance`, bit for bit   */
+  double   s_out;       /* seconds after t0 at which it leaves again, at most T, bit for bit   */
+} cs_leg_interval;
+size_t cs_leg_intervals(cs_engine*, const cs_leg* legs, size_t n, double distance, double speed_max,
+                        const cs_selection* targets, uint64_t* out_counts /* n entries; may be NULL */,
+                        cs_leg_interval* out, size_t cap);
+/* The same on a mesh.  Collective: every rank passes the same legs and gets the single engine's answer, byte for byte.
+ * No halo exchange is made, there are no band records, and distance, speed_max and t1 have no limit: every tile runs ALL
+ * legs against the agents it owns.  One gather carries the per-leg counts (agents are disjoint across tiles, so counts
+ * add, and every rank decides the CS_PAIRS_MAX refusal from them alike); when listing, one more carries each rank's first
+ * rows, and every rank merges the (leg, id)-sorted runs.  The number of collectives depends neither on the crowd nor on
+ * the answer.  A tile that fails makes every rank return SIZE_MAX.  The step's exchange state is not touched. */
+size_t cs_mesh_leg_intervals(cs_mesh*, const cs_leg* legs, size_t n, double distance, double speed_max,
+                             const cs_selection* targets, uint64_t* out_counts, cs_leg_interval* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

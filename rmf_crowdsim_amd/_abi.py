@@ -322,6 +322,15 @@ class LegHit(C.Structure):
     _fields_ = [("id", C.c_uint64), ("s", C.c_double)]
 
 
+class LegInterval(C.Structure):
+    """cs_leg_interval: one row of cs_leg_intervals: agent `id` is within the distance of leg `leg` from t0 + s_in to
+    t0 + s_out (include/crowdstep_state.h)"""
+    _fields_ = [("leg", C.c_uint64), ("id", C.c_uint64), ("s_in", C.c_double), ("s_out", C.c_double)]
+
+
+LEG_INTERVAL_DTYPE = [("leg", "<u8"), ("id", "<u8"), ("s_in", "<f8"), ("s_out", "<f8")]
+
+
 _PAIRS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.POINTER(IdPair), C.POINTER(C.c_double),
                C.c_size_t]
 _CLUSTERS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -332,6 +341,8 @@ _ENCOUNTERS_ARGS = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.POINTER(Se
                     C.POINTER(Encounter), C.c_size_t]
 _RAYS_ARGS = [C.c_void_p, C.POINTER(Ray), C.c_size_t, C.c_double, C.POINTER(Selection), C.POINTER(RayHit)]
 _LEGS_ARGS = [C.c_void_p, C.POINTER(Leg), C.c_size_t, C.c_double, C.c_double, C.POINTER(Selection), C.POINTER(LegHit)]
+_LEG_INTERVALS_ARGS = [C.c_void_p, C.POINTER(Leg), C.c_size_t, C.c_double, C.c_double, C.POINTER(Selection),
+                       C.POINTER(C.c_uint64), C.POINTER(LegInterval), C.c_size_t]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -370,6 +381,8 @@ STATE_SYMBOLS = {
     "cs_mesh_cast_rays": (C.c_size_t, list(_RAYS_ARGS)),
     "cs_leg_conflicts": (C.c_size_t, list(_LEGS_ARGS)),
     "cs_mesh_leg_conflicts": (C.c_size_t, list(_LEGS_ARGS)),
+    "cs_leg_intervals": (C.c_size_t, list(_LEG_INTERVALS_ARGS)),
+    "cs_mesh_leg_intervals": (C.c_size_t, list(_LEG_INTERVALS_ARGS)),
 }
 
 

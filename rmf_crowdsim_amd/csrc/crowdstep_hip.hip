@@ -29,6 +29,7 @@
 //   cs_encounters.hip.inc     the pairs that come within a distance of one another inside a time horizon (the same header)
 //   cs_rays.hip.inc           rays against the crowd: the first agent each ray hits, and where (the same header)
 //   cs_legs.hip.inc           timed path legs against the moving crowd: who comes within a distance first (the same header)
+//   cs_leg_intervals.hip.inc  the same legs, the complete list: every agent that enters a leg, when it enters and leaves
 //   this file                 includes + the extern "C" boundary
 //
 // Device state is f32 and CELL-RELATIVE: an agent is (stored cell, offset from
@@ -1271,3 +1272,4 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_encounters.hip.inc"
 #include "cs_rays.hip.inc"
 #include "cs_legs.hip.inc"
+#include "cs_leg_intervals.hip.inc"

@@ -188,27 +188,27 @@ namespace {
 
 const cs_leg_hit kLegMiss = {CS_NO_HIT, std::numeric_limits<double>::infinity()};
 
-// the refusals of the header (3); the text names the first bad leg
-int legs_check(std::string* error, const cs_leg* legs, size_t n, double distance, double speed_max,
+// the refusals of the header (3), under the name of the call; the text names the first bad leg
+int legs_check(std::string* error, const std::string& call, const cs_leg* legs, size_t n, double distance, double speed_max,
                const cs_selection* targets) {
   if (n > CS_LEGS_MAX) {
-    *error = "leg_conflicts: more legs than CS_LEGS_MAX = 1048576 in one call";
+    *error = call + ": more legs than CS_LEGS_MAX = 1048576 in one call";
     return 3;
   }
   if (n && !legs) {
-    *error = "leg_conflicts: null legs";
+    *error = call + ": null legs";
     return 3;
   }
   if (!(distance >= 0.0)) {
-    *error = "leg_conflicts: the distance is NaN or negative";
+    *error = call + ": the distance is NaN or negative";
     return 3;
   }
   if (!(speed_max >= 0.0)) {
-    *error = "leg_conflicts: speed_max is NaN or negative";
+    *error = call + ": speed_max is NaN or negative";
     return 3;
   }
   if (targets)
-    if (int rc = sel_check(error, targets, "leg_conflicts")) return rc;
+    if (int rc = sel_check(error, targets, call.c_str())) return rc;
   for (size_t k = 0; k < n; ++k) {
     const cs_leg& l = legs[k];
     const char* what = nullptr;
@@ -218,11 +218,23 @@ int legs_check(std::string* error, const cs_leg* legs, size_t n, double distance
     else if (l.t0 < 0.0) what = "its t0 is negative";
     else if (l.t1 < l.t0) what = "its t1 is before its t0";
     if (what) {
-      *error = "leg_conflicts: leg " + std::to_string(k) + ": " + what;
+      *error = call + ": leg " + std::to_string(k) + ": " + what;
       return 3;
     }
   }
   return 0;
+}
+
+// the legs with their `ignore` ids mapped to DEVICE ids, the way the by-id calls map ids: an id no live agent can hold is
+// nobody's
+std::vector<cs_leg> legs_with_device_ids(const cs_engine* e, const cs_leg* legs, size_t n) {
+  std::vector<cs_leg> mine(legs, legs + n);
+  for (cs_leg& l : mine) {
+    uint64_t dev = 0;
+    const bool known = l.ignore != CS_NO_HIT && e->dev_id(l.ignore, &dev) && dev < e->id_limit && dev < 0xFFFFFFFFull;
+    l.ignore = known ? dev : CS_NO_HIT;
+  }
+  return mine;
 }
 
 // All n legs (n > 0) against the agents one engine holds (after sel_begin), into rows[0 .. n) as DEVICE ids.  One upload,
@@ -234,12 +246,7 @@ int legs_run(cs_engine* e, const cs_leg* legs, size_t n, double distance, double
   if (int rc = e->ensure_index()) return rc;
   if (!e->n_slots) return 0;
   const PairsArgs P = pairs_args(e, distance, targets, nullptr);
-  std::vector<cs_leg> mine(legs, legs + n);
-  for (cs_leg& l : mine) {  // the way the by-id calls map ids: an id no live agent can hold is nobody's
-    uint64_t dev = 0;
-    const bool known = l.ignore != CS_NO_HIT && e->dev_id(l.ignore, &dev) && dev < e->id_limit && dev < 0xFFFFFFFFull;
-    l.ignore = known ? dev : CS_NO_HIT;
-  }
+  const std::vector<cs_leg> mine = legs_with_device_ids(e, legs, n);
   PairsScratch sc(e);
   const size_t b_legs = sel_up(n * sizeof(cs_leg));
   unsigned char* p = static_cast<unsigned char*>(sc.get(b_legs + n * sizeof(cs_leg_hit)));
@@ -285,7 +292,7 @@ size_t cs_leg_conflicts(cs_engine* e, const cs_leg* legs, size_t n, double dista
                         const cs_selection* targets, cs_leg_hit* out) {
   if (!e) return SIZE_MAX;
   hipSetDevice(e->device);
-  if (legs_check(&e->error, legs, n, distance, speed_max, targets)) return SIZE_MAX;
+  if (legs_check(&e->error, "leg_conflicts", legs, n, distance, speed_max, targets)) return SIZE_MAX;
   if (sel_begin(e)) return SIZE_MAX;
   if (!n) return 0;
   std::vector<cs_leg_hit> rows;
@@ -300,7 +307,7 @@ size_t cs_mesh_leg_conflicts(cs_mesh* m, const cs_leg* legs, size_t n, double di
                              const cs_selection* targets, cs_leg_hit* out) {
   if (!m) return SIZE_MAX;
   if (m->dead()) return SIZE_MAX;
-  if (legs_check(&m->error, legs, n, distance, speed_max, targets)) return SIZE_MAX;
+  if (legs_check(&m->error, "leg_conflicts", legs, n, distance, speed_max, targets)) return SIZE_MAX;
   if (cs_mesh_synchronize(m)) return SIZE_MAX;
   hipSetDevice(m->device);
   if (!n) return 0;

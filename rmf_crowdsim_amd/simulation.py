@@ -881,6 +881,95 @@ def path_conflict_of(leg_conflicts, waypoints, times, distance, speed_max, ignor
     return int(rows["id"][k]), float(l["t0"]) + s, k, (float(l["x0"]) + float(l["vx"]) * s, float(l["y0"]) + float(l["vy"]) * s)
 
 
+LEG_INTERVAL_DTYPE = np.dtype(_abi.LEG_INTERVAL_DTYPE)
+assert LEG_INTERVAL_DTYPE.itemsize == C.sizeof(_abi.LegInterval) == 32
+
+
+def leg_intervals_call(fn, handle, legs, distance, speed_max, sel, want_counts, cap):
+    """cs_leg_intervals / cs_mesh_leg_intervals with room for `cap` rows -> (the full count, or None on error; the
+    per-leg uint64 counts, or None; the first min(count, cap) rows as a LEG_INTERVAL_DTYPE array).  cap == 0: counts only."""
+    legs = np.ascontiguousarray(legs, dtype=LEG_DTYPE)
+    n, cap = len(legs), max(int(cap), 0)
+    counts = np.zeros(max(n, 1), dtype=np.uint64) if want_counts else None
+    rows = np.zeros(max(cap, 1), dtype=LEG_INTERVAL_DTYPE)
+    got = fn(handle, legs.ctypes.data_as(C.POINTER(_abi.Leg)) if n else None, n, float(distance), float(speed_max),
+             C.byref(sel) if sel is not None else None,
+             counts.ctypes.data_as(C.POINTER(C.c_uint64)) if want_counts else None,
+             rows.ctypes.data_as(C.POINTER(_abi.LegInterval)) if cap else None, cap)
+    if got == _SIZE_MAX:
+        return None, None, rows[:0].copy()
+    return got, (counts[:n].copy() if want_counts else None), rows[:min(got, cap)].copy()
+
+
+def leg_intervals_of(fn, handle, handle_of, err, legs, distance, speed_max, targets, limit):
+    """leg_intervals and count_leg_intervals of Simulation and NativeTileMesh.  limit=None lists every interval (one
+    counting call first), limit=0 only counts -> (count, per-leg counts, rows)"""
+    sel = None if targets is None else selection_struct(targets, handle_of)
+    if limit is None:
+        limit, _, _ = leg_intervals_call(fn, handle, legs, distance, speed_max, sel, False, 0)
+        if limit is None:
+            raise err()
+        if limit > _abi.CS_PAIRS_MAX:
+            limit = 1  # (the listing is refused by the library, with its message: no room is made for it here)
+    n, counts, rows = leg_intervals_call(fn, handle, legs, distance, speed_max, sel, True, limit)
+    if n is None:
+        raise err()
+    return int(n), counts, rows
+
+
+def merge_leg_intervals(rows, n_legs):
+    """The occupied time of each leg: (offsets, spans).  rows: LEG_INTERVAL_DTYPE rows of legs 0 .. n_legs - 1 in any
+    order; spans: float64 (m, 2), the union of the [s_in, s_out] of each leg as disjoint (start, end) in seconds after the
+    leg's t0, ascending in time, overlapping and touching spans merged; the spans of leg k are
+    spans[offsets[k]:offsets[k + 1]] (offsets: int64, n_legs + 1 entries).  Pure numpy."""
+    rows = np.asarray(rows, dtype=LEG_INTERVAL_DTYPE)
+    n_legs = int(n_legs)
+    if len(rows) and int(rows["leg"].max()) >= n_legs:
+        raise ValueError("merge_leg_intervals: a row of a leg beyond n_legs")
+    order = np.lexsort((rows["s_out"], rows["s_in"], rows["leg"]))
+    leg, lo, hi = rows["leg"][order].astype(np.int64), rows["s_in"][order], rows["s_out"][order]
+    first = np.ones(len(rows), dtype=bool)  # does row i begin a span: another leg, or later than all that came before
+    if len(rows) > 1:
+        # the largest end so far within the leg, on the ranks of the times (integers: exact, so touching spans merge);
+        # legs are kept apart by an offset larger than any rank
+        times, rank = np.unique(np.concatenate([lo, hi]), return_inverse=True)
+        r_lo, r_hi, step = rank[:len(rows)], rank[len(rows):], len(times) + 1
+        reach = np.maximum.accumulate(r_hi + leg * step)[:-1] - leg[1:] * step
+        first[1:] = (leg[1:] != leg[:-1]) | (r_lo[1:] > reach)
+    begin = np.nonzero(first)[0]
+    spans = np.zeros((len(begin), 2), dtype=np.float64)
+    if len(begin):
+        spans[:, 0] = lo[begin]
+        spans[:, 1] = np.maximum.reduceat(hi, begin)
+    offsets = np.zeros(n_legs + 1, dtype=np.int64)
+    np.cumsum(np.bincount(leg[begin], minlength=n_legs), out=offsets[1:])
+    return offsets, spans
+
+
+def free_spans(offsets, spans, t0, t1):
+    """The complement of merge_leg_intervals' spans inside each leg: per leg a list of (start, end) ABSOLUTE times inside
+    [t0[k], t1[k]] during which nobody is within the distance, ascending; spans of zero length are left out."""
+    out = []
+    for k in range(len(offsets) - 1):
+        a, b, free = float(t0[k]), float(t1[k]), []
+        at = a
+        for s, e in spans[offsets[k]:offsets[k + 1]]:
+            if a + float(s) > at:
+                free.append((at, a + float(s)))
+            at = max(at, a + float(e))
+        if b > at:
+            free.append((at, b))
+        out.append(free)
+    return out
+
+
+def free_intervals_of(leg_intervals, points, t0, t1, distance, speed_max, ignore, targets):
+    """free_intervals of Simulation and NativeTileMesh over their leg_intervals"""
+    legs = legs_array(points, (0.0, 0.0), t0, t1, ignore)
+    offsets, spans = merge_leg_intervals(leg_intervals(legs, distance, speed_max, targets=targets), len(legs))
+    return free_spans(offsets, spans, legs["t0"], legs["t1"])
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -1342,6 +1431,31 @@ class Simulation:
         conflict: who, the time t = t0 + s from now, the leg (counted without the dropped ones) and where the probe is
         then."""
         return path_conflict_of(self.leg_conflicts, waypoints, times, distance, speed_max, ignore, targets)
+
+    def leg_intervals(self, legs, distance, speed_max, *, targets=None, limit=None):
+        """Everybody who comes within `distance` of each timed leg, and when, on the device (cs_leg_intervals): the
+        arguments of leg_conflicts.  Returns a structured array (leg, id, s_in, s_out), ascending by (leg, id): agent id
+        is within the distance of leg `leg` from t0 + s_in to t0 + s_out, s_out at most t1 - t0 (equal: it is still there
+        when the leg ends); a row for exactly the (leg, agent) that conflict by the rule of leg_conflicts, s_in that
+        rule's s, both times bit for bit the f64 rule of include/crowdstep_state.h.  limit: at most that many rows (the
+        first ones); None lists all, and above _abi.CS_PAIRS_MAX raises, count_leg_intervals has no limit.  Changes
+        nothing.  merge_leg_intervals turns the rows into the occupied spans of each leg."""
+        fn = state_fn(self._lib, self.backend, "cs_leg_intervals", "leg_intervals")
+        return leg_intervals_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, legs, distance,
+                                speed_max, targets, limit)[2]
+
+    def count_leg_intervals(self, legs, distance, speed_max, *, targets=None):
+        """The number of rows of leg_intervals(...) per leg (uint64, one entry per leg), from one pass that lists
+        nothing, exact whatever its size."""
+        fn = state_fn(self._lib, self.backend, "cs_leg_intervals", "leg_intervals")
+        return leg_intervals_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, legs, distance,
+                                speed_max, targets, 0)[1]
+
+    def free_intervals(self, points, t0, t1, distance, speed_max, *, ignore=None, targets=None):
+        """When is each point free of the crowd: one waiting leg per point of points (n, 2) from t0 to t1 (scalars or one
+        value per point, seconds from now) in one leg_intervals call.  Returns, per point, the list of (start, end)
+        absolute times inside [t0, t1] during which nobody slower than speed_max is within `distance` of it, ascending."""
+        return free_intervals_of(self.leg_intervals, points, t0, t1, distance, speed_max, ignore, targets)
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

@@ -844,6 +844,27 @@ class NativeTileMesh:
         from .simulation import path_conflict_of
         return path_conflict_of(self.leg_conflicts, waypoints, times, distance, speed_max, ignore, targets)
 
+    def leg_intervals(self, legs, distance, speed_max, *, targets=None, limit=None):
+        """Simulation.leg_intervals on the mesh (cs_mesh_leg_intervals): the single engine's answer, byte for byte
+        (collective in the distributed form).  Every tile runs all legs against the agents it owns; one gather carries the
+        per-leg counts, one more the rows, which every rank merges by (leg, id)."""
+        from .simulation import leg_intervals_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_leg_intervals", "leg_intervals")
+        return leg_intervals_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, legs, distance, speed_max,
+                                targets, limit)[2]
+
+    def count_leg_intervals(self, legs, distance, speed_max, *, targets=None):
+        """Simulation.count_leg_intervals on the mesh (collective in the distributed form): only counts travel."""
+        from .simulation import leg_intervals_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_leg_intervals", "leg_intervals")
+        return leg_intervals_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, legs, distance, speed_max,
+                                targets, 0)[1]
+
+    def free_intervals(self, points, t0, t1, distance, speed_max, *, ignore=None, targets=None):
+        """Simulation.free_intervals on the mesh (one leg_intervals call; collective in the distributed form)."""
+        from .simulation import free_intervals_of
+        return free_intervals_of(self.leg_intervals, points, t0, t1, distance, speed_max, ignore, targets)
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
