@@ -14,9 +14,7 @@ import numpy as np
 from rmf_crowdsim_amd import _abi
 from rmf_crowdsim_amd.simulation import LEG_DTYPE, LEG_INTERVAL_DTYPE, legs_array
 from close_pairs_reference import SIZE_MAX, last_error, roles, takes_part
-from legs_reference import rule
-
-BLOCK = 256
+from legs_reference import block_of, rule
 
 
 def leaves(x, y, vx, vy, legs, distance, s_in):
@@ -60,6 +58,7 @@ def intervals(records, grid, legs, distance, speed_max, targets=None, stats=None
     vy = records["vy"][part].astype(np.float32).astype(np.float64)[order]
     counts = np.zeros(len(legs), dtype=np.uint64)
     out, same = [], 0
+    BLOCK = block_of(len(ids))
     for lo in range(0, len(legs) if len(ids) else 0, BLOCK):
         block = legs[lo:lo + BLOCK]
         hit, s_in, _ = rule(x, y, vx, vy, block, distance, speed_max)

@@ -14,9 +14,15 @@ from rmf_crowdsim_amd import _abi
 from rmf_crowdsim_amd.simulation import LEG_DTYPE, LEG_HIT_DTYPE, legs_array
 from close_pairs_reference import SIZE_MAX, last_error, roles, takes_part
 
-BLOCK = 256
+BLOCK = 256  # legs of one block, at most
 NO_HIT = np.uint64(_abi.CS_NO_HIT)
 INF = np.float64(np.inf)
+
+
+def block_of(n_agents):
+    """The legs taken at a time: the [legs, agents] temporaries of a block stay near 64K numbers each, in cache (the answer
+    does not depend on it: every operation is per (leg, agent), every reduction per leg)."""
+    return max(1, min(BLOCK, 65536 // max(n_agents, 1)))
 
 
 def rule(x, y, vx, vy, legs, distance, speed_max):
@@ -66,6 +72,7 @@ def conflicts(records, grid, legs, distance, speed_max, targets=None, stats=None
     out = np.zeros(len(legs), dtype=LEG_HIT_DTYPE)
     out["id"], out["s"] = NO_HIT, INF
     not_nearest = 0
+    BLOCK = block_of(len(ids))
     for lo in range(0, len(legs) if len(ids) else 0, BLOCK):
         block = legs[lo:lo + BLOCK]
         hit, s, _ = rule(x, y, vx, vy, block, distance, speed_max)

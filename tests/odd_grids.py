@@ -3,7 +3,8 @@ on (one-sided, one cell wide or high, two-launch scans, cell indices near 2^31, 
 an offset that dwarfs the cell) and one function per query family that asks the engine (or a mesh) and compares the
 answer with the numpy restatement on `records`, its OWN read_agents(), exactly as the query tests do on their square
 grids of 2 m cells.  Ids, counts, orders and the bits of every f64 are exact; the raster's velocity sums keep
-field_reference.tolerance.
+field_reference.tolerance.  The families: selections, rasters, the distance queries, encounters, rays, and the timed legs
+(ask_legs for cs_leg_conflicts, ask_intervals for cs_leg_intervals); ask_everything asks them all.
 
 x runs over the grid's ny = height / cell rows, y over one row's nx = width / cell columns; the flat cell index is
 row * nx + column (tests/test_gpu_large_grids.py)."""
@@ -15,11 +16,15 @@ import close_pairs_reference as pairs_ref
 import clusters_reference as clusters_ref
 import encounters_reference as encounters_ref
 import field_reference as field_ref
+import leg_intervals_reference as intervals_ref
+import legs_reference as legs_ref
 import neighbours_reference as neighbours_ref
 import rays_reference as rays_ref
 from rmf_crowdsim_amd import StubHighLevelPlan, _abi, scenes
 from select_reference import count, pred, select, selection
 from test_gpu_large_grids import BIG, LP, SCAN_TILE, WALK, _cluster, _grid, _line_crowd, tile_crowd
+from test_gpu_leg_conflicts import leg_sets, speeds
+from test_gpu_leg_intervals import interval_legs
 from test_gpu_rays import ray_sets
 
 INF = float("inf")
@@ -233,6 +238,156 @@ def ask_long_axis_rays(sim, sc, rec, name, radius=0.2):
     return want
 
 
+# ---- timed legs: cs_leg_conflicts and cs_leg_intervals ------------------------------------------------------------------
+# May a leg be asked at speed_max = +inf (or distance = +inf)?  Its reach is then without bound and its wave visits every
+# row of the grid one after the other: the two-million-row corridors are not walked whole.
+WHOLE_WALK = {"corridor": False, "corridor2": False, "strip": True, "strip2": True, "tall5": True, "two-launch": True,
+              "odd-cell": True, "odd-far": True, "corner 64": True, f"corner {BIG}": True}
+# k_leg_intervals takes the columns of a row as one run of slots, k_leg_conflicts 16 columns at a time: without a reach it
+# looks at 4,097 x 257 = 1.05M chunks of the two-launch grid, one after the other, and at 46,340 x 2,897 = 134M of the
+# 31-bit grid, whatever the number of legs (a leg is a wave): with it the corner test took 114 s on an MI355X, 9 s
+# without.  Those two grids are walked whole by cs_leg_intervals only.
+WHOLE_WALK_CONFLICTS = dict(WHOLE_WALK, **{"two-launch": False, f"corner {BIG}": False})
+# the random legs of leg_sets where they are not its 500: the restatement is legs x agents, and the tests of the
+# two-launch grid take about a second in all
+SEGMENTS = {"two-launch": 60}
+
+
+def long_axis_floor(sc):
+    """Must somebody stand in the way of the long-axis legs?  Not on the square grids whose crowd is a few clusters far
+    apart (the legs still run there)."""
+    return sc.name != "two-launch" and not sc.name.startswith("corner")
+
+
+def has_standers(sc):
+    """does a part of the scene's crowd prefer to stand still (the clusters in the corners of the square grids)"""
+    return any(tuple(vel) == (0.0, 0.0) for _, vel in sc.parts)
+
+
+def walking_pace(rec):
+    """The median speed of those who walk (faster than half the fastest): where everybody walks, the median speed, which
+    lies between the two walking speeds of a scene; a few dozen agents written to a standstill do not move it onto the
+    slower of the two (the filter is strict: it would admit them alone)."""
+    s = speeds(rec)
+    return float(np.median(s[s > 0.5 * s.max()]))
+
+
+def long_axis_legs(sc, rec, stretch=800.0):
+    """16 legs along the grid's long axis (y on a grid wider than high) from 5 m outside its low end, or from 200 m before
+    the crowd where that is nearer, through the first `stretch` metres of the crowd in 8 s; spread over the crowd's
+    extent across that axis and 2 m to either side of it"""
+    gx0, gx1, gy0, gy1 = pairs_ref.rectangle(sc.grid)
+    k = np.arange(16) / 15.0
+    along, across, g_lo = (rec["x"], rec["y"], gx0) if sc.rows >= sc.cols else (rec["y"], rec["x"], gy0)
+    begin = max(g_lo - 5.0, float(along.min()) - 200.0)
+    run = (float(along.min()) - begin) + min(stretch, float(along.max() - along.min())) + 5.0
+    side = (float(across.min()) - 2.0) + k * (float(across.max() - across.min()) + 4.0)
+    if sc.rows >= sc.cols:
+        return legs_ref.legs_array(np.column_stack([np.full(16, begin), side]), (run / 8.0, 0.0), 0.0, 8.0)
+    return legs_ref.legs_array(np.column_stack([side, np.full(16, begin)]), (0.0, run / 8.0), 0.0, 8.0)
+
+
+def _with_long_axis(sc, rec, legs, extra, crowd=None):
+    """legs, then `extra` (a test's own legs), then the 16 long-axis legs: they are the last 16 of every set.  crowd: the
+    records the long-axis legs are laid through, where a test has written agents far from the crowd (None: rec)"""
+    return np.concatenate([legs] + ([] if extra is None else [extra]) + [long_axis_legs(sc, rec if crowd is None else crowd)])
+
+
+def asked_legs(sc, legs, extra=None, conflicts=False):
+    """The legs of each ask of ask_legs (conflicts=True) and ask_intervals: all of them twice and, where the grid allows
+    the whole walk, the first hundred, a test's own and the long-axis legs, which are asked at speed_max = +inf"""
+    n = 0 if extra is None else len(extra)
+    whole = (WHOLE_WALK_CONFLICTS if conflicts else WHOLE_WALK)[sc.name]
+    return [legs, legs] + ([np.concatenate([legs[:100], legs[len(legs) - 16 - n:]])] if whole else [])
+
+
+def conflict_leg_set(sc, rec, extra=None, crowd=None):
+    return _with_long_axis(sc, rec, leg_sets(rec, sc.grid, segments=SEGMENTS.get(sc.name, 500)), extra, crowd)
+
+
+def interval_leg_set(sc, rec, extra=None, crowd=None):
+    return _with_long_axis(sc, rec, interval_legs(rec, sc.grid, segments=SEGMENTS.get(sc.name, 500)), extra, crowd)
+
+
+def ask_legs(sim, sc, rec, name, want=None, legs=None, extra=None, crowd=None):
+    """The leg sets and the long-axis legs at distances of 0.4 and 0.8 cells, the second with the speed filter between
+    the two walking speeds of the scene; where the grid allows, the first hundred legs at speed_max = +inf (the whole
+    walk).  The classes by the restatement alone (printed, then asserted), then the engine.  -> the restatement's rows.
+    legs: the whole set where it is not made here (its last 16 the long-axis legs); extra: legs of the test's own, asked
+    with the others; crowd: the records the long-axis legs are laid through (None: rec)."""
+    pace = walking_pace(rec)
+    if legs is None:
+        legs = conflict_leg_set(sc, rec, extra, crowd)
+    asks = list(zip(asked_legs(sc, legs, extra, conflicts=True), (0.4 * sc.cell, 0.8 * sc.cell, 0.4 * sc.cell), (2.0, pace, INF)))
+    out = []
+    for k, (l, distance, speed_max) in enumerate(asks):
+        w = legs_ref.conflicts(rec, sc.grid, l, distance, speed_max) if want is None else want[k]
+        moving, still, miss = legs_ref.classes(w)
+        along = int((w["id"][-16:] != legs_ref.NO_HIT).sum())
+        print(f"{name}, legs {(distance, speed_max)}: restatement alone: {still} conflicts at s == 0, {moving} at s > 0, "
+              f"{miss} misses; {along} of the 16 long-axis legs conflict")
+        if k == 1 and has_standers(sc):
+            # (walkers of one speed and standers: the median speed admits the standers alone, and few legs pass them.
+            # The first query carries the classes; this one is compared all the same)
+            assert miss >= 5
+        else:
+            assert (still >= 5 and moving >= 5 and miss >= 5) if k < 2 else (still + moving >= 5 and miss >= 1)
+        legs_ref.agree(sim, rec, sc.grid, l, distance, speed_max, name=f"{name}, legs {(distance, speed_max)}", want=w)
+        out.append(w)
+    if long_axis_floor(sc):
+        assert (out[0]["id"][-16:] != legs_ref.NO_HIT).sum() >= 2  # (somebody stands in the way of the long-axis legs)
+    return out
+
+
+def interval_queries(sc, rec):
+    """(distance, speed_max) of the interval queries: everybody slower than 2 m/s within 0.4 cell, the speed filter
+    between the slowest and the fastest within 0.8 cell, and (where the grid allows the whole walk) everybody"""
+    return [(0.4 * sc.cell, 2.0), (0.8 * sc.cell, _speeds(rec)[1]), (0.4 * sc.cell, INF)]
+
+
+def intervals_alone(sc, rec, name, legs, extra=None):
+    """The restatement ALONE on the asks of ask_intervals: the classes of every ask printed, then the floors asserted.
+    The first query carries them all; the second is there for its filter (where somebody stands still it admits the
+    standers alone, who enter few legs later than at once), the third for the walk without a reach.
+    -> [(legs, distance, speed_max)], [(rows, counts)]"""
+    asks = [(l, d, v) for l, (d, v) in zip(asked_legs(sc, legs, extra), interval_queries(sc, rec))]
+    out = []
+    for k, (l, distance, speed_max) in enumerate(asks):
+        stats = {}
+        rows, counts = intervals_ref.intervals(rec, sc.grid, l, distance, speed_max, stats=stats)
+        along = int((counts[-16:] > 0).sum())
+        print(f"{name}, intervals {(distance, speed_max)}: restatement alone: {len(rows)} rows, {stats}; {along} of the 16 "
+              f"long-axis legs have rows")
+        if k == 0:
+            assert min(stats["at_start"], stats["later"], stats["leaves"], stats["stays"], stats["same_velocity"]) >= 15, stats
+            assert stats["crowded_legs"] >= 10 and stats["free_legs"] >= 5, stats
+            assert along >= 2 or not long_axis_floor(sc)
+        elif k == 1:
+            assert len(rows) > 0 and stats["at_start"] >= 15, stats
+        else:
+            assert len(rows) > 0
+        out.append((rows, counts))
+    return asks, out
+
+
+def ask_intervals(sim, sc, rec, name, want=None, legs=None, extra=None, crowd=None):
+    """interval_legs and the long-axis legs, from `rec`, at interval_queries and, where the grid allows, the first hundred
+    legs at speed_max = +inf (the whole walk): the classes by the restatement alone (intervals_alone), then the engine:
+    ids, per-leg counts and the bits of s_in and s_out through leg_intervals_reference.agree.  -> the restatement's
+    [(rows, counts)].  want: that list, where a test has it already (a mesh after the engine: the floors were asserted
+    then); legs, extra, crowd: as for ask_legs."""
+    if legs is None:
+        legs = interval_leg_set(sc, rec, extra, crowd)
+    if want is None:
+        asks, want = intervals_alone(sc, rec, name, legs, extra)
+    else:
+        asks = [(l, d, v) for l, (d, v) in zip(asked_legs(sc, legs, extra), interval_queries(sc, rec))]
+    for (l, distance, speed_max), w in zip(asks, want):
+        intervals_ref.agree(sim, rec, sc.grid, l, distance, speed_max, name=f"{name}, intervals {(distance, speed_max)}",
+                            want=w)
+    return want
+
+
 def region_selections(sc, rec):
     """The cells of the last row, of the last column, the quadrant from the median agent to the high corner, a circle
     round the agent in the first occupied cell, the faster walkers by a speed term."""
@@ -344,12 +499,18 @@ def ask_fields(sim, sc, rec, name, monkeypatch, at_end=None):
     monkeypatch.delenv("CS_FIELD_LDS_BYTES", raising=False)
 
 
-def ask_everything(sim, sc, rec, name, monkeypatch, scale=1.0, longest=INF, ray_floors=True, at_end=None):
+def ask_everything(sim, sc, rec, name, monkeypatch, scale=1.0, longest=INF, ray_floors=True, at_end=None, legs=True,
+                   extra_legs=None, legs_crowd=None):
+    """legs=False: the test asks the two leg calls itself, with legs of its own; extra_legs, legs_crowd: the extra and
+    crowd of ask_legs and ask_intervals"""
     ask_selections(sim, sc, rec, name, at_end)
     ask_fields(sim, sc, rec, name, monkeypatch, at_end)
     pairs = ask_distance_queries(sim, sc, rec, name)
     rows = ask_encounters(sim, sc, rec, name, scale)
     ask_rays(sim, sc, rec, name, scale, longest, floors=ray_floors)
+    if legs:
+        ask_legs(sim, sc, rec, name, extra=extra_legs, crowd=legs_crowd)
+        ask_intervals(sim, sc, rec, name, extra=extra_legs, crowd=legs_crowd)
     assert sim.read_agents().tobytes() == rec.tobytes(), name  # (asking changes nothing)
     return pairs, rows
 
@@ -446,6 +607,88 @@ def check_edges(sc, rec, w, ids, outsiders):
                       for c, o in (("x", ox), ("y", oy)))
     print(f"{sc.name}: {through_f32} coordinates of participants differ from offset + (float32)(coordinate - offset)")
     assert through_f32 >= 1
+
+
+def edge_legs(sc, rec, w):
+    """Legs made for the agents edge_agents wrote, from where `rec` holds them: for each of the eight edge agents and
+    each outsider a wait of 1.5 s 0.1 cell beside it, on the side away from the grid's middle (outside the rectangle for
+    an agent on a low edge), then for each a leg of 3 s that starts 3 cells outside the grid from it and is where the
+    agent will be after 2 s.  Nobody is ignored.  -> (legs, the number of waits)"""
+    at = {int(i): j for j, i in enumerate(rec["id"])}
+    who = rec[[at[int(i)] for i in np.concatenate([w["id"][:8], w["id"][16:]])]]
+    gx0, gx1, gy0, gy1 = pairs_ref.rectangle(sc.grid)
+
+    def away(p, lo, hi):  # -1 by the low edge (or below it), +1 by the high edge, 0 in the middle
+        return np.where(p < lo + 0.25 * (hi - lo), -1.0, np.where(p > hi - 0.25 * (hi - lo), 1.0, 0.0))
+
+    out = np.column_stack([away(who["x"], gx0, gx1), away(who["y"], gy0, gy1)])
+    assert (np.abs(out).sum(axis=1) >= 1).all()
+    p = np.column_stack([who["x"], who["y"]])
+    v = np.column_stack([who["vx"].astype(np.float32).astype(np.float64), who["vy"].astype(np.float32).astype(np.float64)])
+    waits = legs_ref.legs_array(p + 0.1 * sc.cell * out, (0.0, 0.0), 0.0, 1.5)
+    start = p + 3.0 * sc.cell * out
+    inward = legs_ref.legs_array(start, ((p + 2.0 * v) - start) / 2.0, 0.0, 3.0)
+    return np.concatenate([waits, inward]), len(waits)
+
+
+def check_edge_legs(sc, rec, w, ids, legs):
+    """By the restatement alone, at the first interval query: at least four of the eight edge agents are rows of the edge
+    legs, the outsiders are rows of no leg.  -> (rows, counts)"""
+    distance, speed_max = interval_queries(sc, rec)[0]
+    rows, counts = intervals_ref.intervals(rec, sc.grid, legs, distance, speed_max)
+    listed = int(np.isin(ids.astype(np.uint64), rows["id"]).sum())
+    print(f"{sc.name}: restatement alone: {len(rows)} rows of the {len(legs)} edge legs; {listed} of the 8 edge agents are "
+          f"rows, {int(np.isin(rows['id'], w['id'][16:].astype(np.uint64)).sum())} rows are outsiders")
+    assert listed >= 4 and not np.isin(rows["id"], w["id"][16:].astype(np.uint64)).any()
+    return rows, counts
+
+
+def ask_legs_wider_than_the_grid(sim, sc, rec, w, waits, name):
+    """Both leg calls on the waits of edge_legs, each ignoring the agent it stands beside, at speed_max = +inf and a
+    distance of twice the grid's width and of +inf: every participant but the ignored one is a row of every leg, from 0 to
+    T; the first of them by id is the conflict."""
+    part = pairs_ref.takes_part(rec, sc.grid)
+    waits = waits.copy()
+    waits["ignore"] = np.concatenate([w["id"][:8], w["id"][16:]]).astype(np.uint64)
+    less = np.isin(waits["ignore"], rec["id"][part].astype(np.uint64)).astype(np.uint64)
+    for distance in (2.0 * sc.grid["width"], INF):
+        rows, counts = intervals_ref.agree(sim, rec, sc.grid, waits, distance, INF,
+                                           name=f"{name}, intervals wider than the grid: {distance}")
+        assert 0 < less.sum() < len(waits) and (counts == np.uint64(part.sum()) - less).all()
+        assert (rows["s_in"] == 0.0).all() and (rows["s_out"] == 1.5).all()
+        hits = legs_ref.agree(sim, rec, sc.grid, waits, distance, INF, name=f"{name}, legs wider than the grid: {distance}")
+        assert (hits["id"] != legs_ref.NO_HIT).all() and (hits["s"] == 0.0).all()
+
+
+def ask_python_surface_of_the_legs(sim, sc, rec, name, crowd, distance=0.3):
+    """Simulation.free_intervals on 50 spots 0.3 m beside agents of `crowd` (records of `rec`: the lattice, without the
+    agents written onto the edges) against the complement of the restatement's rows, and Simulation.path_conflict on one
+    path through the crowd against the first conflict of its legs by the restatement."""
+    from rmf_crowdsim_amd.simulation import free_spans, merge_leg_intervals, paths_legs
+    speed_max = 2.0
+    part = _sorted(crowd[pairs_ref.takes_part(crowd, sc.grid)])
+    who = part[np.linspace(0, len(part) - 1, 50).astype(np.int64)]
+    spots = np.column_stack([who["x"] + 0.3, who["y"]])
+    waits = legs_ref.legs_array(spots, (0.0, 0.0), 0.5, 4.0)
+    rows, _ = intervals_ref.intervals(rec, sc.grid, waits, distance, speed_max)
+    want = free_spans(*merge_leg_intervals(rows, len(waits)), waits["t0"], waits["t1"])
+    kinds = [len(f) for f in want]
+    print(f"{name}, free_intervals: restatement alone: {len(rows)} rows; {kinds.count(0)} of 50 spots never free, "
+          f"{sum(f == [(0.5, 4.0)] for f in want)} always")
+    assert len(rows) >= 50 and sum(0 < len(f) and f != [(0.5, 4.0)] for f in want) >= 10  # (free for a part of the time)
+    assert sim.free_intervals(spots, 0.5, 4.0, distance, speed_max) == want, name
+    lo, hi = np.array([part["x"].min(), part["y"].min()]), np.array([part["x"].max(), part["y"].max()])
+    mid = lo + np.array([0.31, 0.43]) * (hi - lo)
+    path = (np.array([lo - 3.0, mid, mid, hi + 3.0]), np.array([0.0, 4.0, 5.0, 12.0]))  # (the second leg is a wait)
+    legs, _ = paths_legs([path])
+    hits = legs_ref.conflicts(rec, sc.grid, legs, distance, speed_max)
+    first = np.nonzero(hits["id"] != legs_ref.NO_HIT)[0]
+    print(f"{name}, path_conflict: restatement alone: legs {first.tolist()} of {len(legs)} conflict")
+    assert len(legs) == 3 and len(first) >= 1
+    k = int(first[0])
+    l, s = legs[k], float(hits["s"][k])
+    want = (int(hits["id"][k]), float(l["t0"]) + s, k, (float(l["x0"]) + float(l["vx"]) * s, float(l["y0"]) + float(l["vy"]) * s))
+    assert sim.path_conflict(*path, distance, speed_max) == want, name
 
 
 # ---- meshes -----------------------------------------------------------------------------------------------------------

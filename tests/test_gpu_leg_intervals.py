@@ -28,10 +28,10 @@ MEDIAN = "the median speed"
 QUERIES = [(0.5, INF), (1.0, MEDIAN), (0.2, INF)]  # (distance, speed_max)
 
 
-def interval_legs(rec, grid, seed=7):
-    """The leg sets of the leg-conflict tests and legs made for the rows of equal velocity: 64 legs that walk along with an
-    agent (ids spread over the crowd), 0.1 m beside it with its widened velocity, and waits 0.1 m beside up to 20 agents
-    that stand still."""
+def interval_legs(rec, grid, seed=7, segments=500):
+    """The leg sets of the leg-conflict tests (`segments` random legs) and legs made for the rows of equal velocity: 64 legs
+    that walk along with an agent (ids spread over the crowd), 0.1 m beside it with its widened velocity, and waits 0.1 m
+    beside up to 20 agents that stand still."""
     part = rec[takes_part(rec, grid)]
     part = part[np.argsort(part["id"])]
     with_ = part[(np.arange(64) * 2 + 1) * len(part) // 128]
@@ -40,7 +40,7 @@ def interval_legs(rec, grid, seed=7):
     along = legs_array(np.column_stack([with_["x"] + v[:, 0] * t0 + 0.1, with_["y"] + v[:, 1] * t0]), v, t0, t0 + 2.0)
     still = part[speeds(part) == 0.0][:20]
     waits = legs_array(np.column_stack([still["x"], still["y"] + 0.1]), (0.0, 0.0), 0.0, 1.5) if len(still) else along[:0]
-    return np.concatenate([leg_sets(rec, grid, seed), along, waits])
+    return np.concatenate([leg_sets(rec, grid, seed, segments), along, waits])
 
 
 def check_query(sim, rec, grid, distance, speed_max, name, sel=None, cols=(None, None, None), floors=True, legs=None):
@@ -69,6 +69,73 @@ def first_of_each_leg(rows, n_legs):
     head = np.nonzero(np.concatenate([[True], leg[1:] != leg[:-1]]))[0] if len(rows) else np.zeros(0, dtype=np.int64)
     out["id"][leg[head]], out["s"][leg[head]] = rows["id"][order][head], rows["s_in"][order][head]
     return out
+
+
+MANY_LEGS = 2 ** 17 + 3  # leg indices of 18 bits: the sort of a listing runs five passes over the leg half of its keys
+
+
+def many_legs(rec, grid, n=MANY_LEGS, seed=17):
+    """n legs drawn from interval_legs(rec, grid): the same few hundred legs under indices up to n - 1"""
+    pool = interval_legs(rec, grid)
+    return pool[np.random.default_rng(seed).integers(0, len(pool), n)]
+
+
+def thin(sim, rec, every):
+    """Remove all agents but every `every`-th of `rec` by id -> the records left (the restatement is legs x agents)"""
+    ids = np.sort(rec["id"])
+    sim.remove_agents_by_id(np.setdiff1d(ids, ids[::every]).tolist())
+    left = sim.read_agents()
+    assert sorted(left["id"].tolist()) == ids[::every].tolist()
+    return left
+
+
+def long_listing_alone(left, grid, legs, distance, speed_max, name):
+    """The restatement ALONE on a listing of many legs (printed, then asserted): at least 1,000 rows at legs from 2^16 on,
+    rows in at least 16 of the groups leg >> 13.  -> (rows, counts)"""
+    rows, counts = intervals(left, grid, legs, distance, speed_max)
+    high, groups = int((rows["leg"] >= 2 ** 16).sum()), len(np.unique(rows["leg"].astype(np.int64) >> 13))
+    print(f"  {name}: restatement alone: {len(legs)} legs against {len(left)} agents: {len(rows)} rows, {high} of them at "
+          f"legs from 2^16 on, in {groups} groups of 2^13 legs")
+    assert high >= 1000 and groups >= 16
+    return rows, counts
+
+
+def check_long_listing(sim, left, grid, legs, distance, speed_max, name, want):
+    """An engine (or a mesh) against the restatement's (rows, counts) of a long listing: listing and counting, a cap at
+    half the rows, the Python surface's counts, and cs_leg_conflicts on the same legs against the first row of each."""
+    rows, counts = want
+    agree(sim, left, grid, legs, distance, speed_max, name=name, want=want)
+    cap = len(rows) // 2
+    got, per_leg, out = call(sim, legs, distance, speed_max, cap=cap)
+    assert got == len(rows) and per_leg.tobytes() == counts.tobytes()
+    assert out[:cap].tobytes() == rows[:cap].tobytes() and (out[cap:].view(np.uint8) == 0xAB).all()
+    assert sim.count_leg_intervals(legs, distance, speed_max).tobytes() == counts.tobytes()
+    hits, first = call_conflicts(sim, legs, distance, speed_max)
+    assert hits == int((counts > 0).sum())
+    assert first[:len(legs)].tobytes() == first_of_each_leg(rows, len(legs)).tobytes()
+
+
+@pytest.mark.parametrize("where", ["a square grid", "odd-cell"])
+def test_a_listing_of_two_to_the_17_legs(where):
+    """2^17 + 3 legs against about 300 agents: rows whose leg index needs bits 16 and 17 of the key's leg half (the other
+    listings of this module have at most 700 legs, 10 bits), on the crossing crowd's grid of 2 m cells and on the 0.7 m
+    cells of tests/odd_grids.py.  The legs are made from the whole crowd, which is then thinned."""
+    if where == "odd-cell":
+        import odd_grids as og
+        sc = og.scene(where)
+        a, grid, distance = og.stepped(sc, lambda g: Simulation(LocationHash2D(**g))), sc.grid, 0.4 * sc.cell
+        every = 7
+    else:
+        a, led, _, grid = _scene(0, 1024)
+        _advance(a, led, 40)
+        distance, every = 0.5, 3
+    rec = a.read_agents()
+    legs = many_legs(rec, grid)
+    left = thin(a, rec, every)
+    assert 250 <= len(left) <= 350 and takes_part(left, grid).all()
+    want = long_listing_alone(left, grid, legs, distance, 2.0, where)
+    check_long_listing(a, left, grid, legs, distance, 2.0, where, want)
+    assert a.read_agents().tobytes() == left.tobytes()
 
 
 @pytest.mark.parametrize("flags", FLAGS)

@@ -13,7 +13,7 @@ from select_reference import selection
 from test_gpu_agent_write import _add_crossing
 from test_gpu_encounters_mesh import _crowd
 from test_gpu_leg_conflicts_mesh import _cut_legs
-from test_gpu_leg_intervals import interval_legs
+from test_gpu_leg_intervals import check_long_listing, interval_legs, long_listing_alone, many_legs, thin
 
 pytestmark = pytest.mark.gpu
 INF = float("inf")
@@ -84,6 +84,29 @@ def test_a_mesh_lists_the_intervals_as_one_engine():
         for _ in range(5):
             t.step(0.05)
     assert mesh.read_agents().tobytes() == twin.read_agents().tobytes()
+
+
+def test_a_mesh_lists_two_to_the_17_legs_as_one_engine():
+    """The long listing of tests/test_gpu_leg_intervals.py on 2 x 2 tiles: every tile sorts its own rows by keys whose
+    leg half has 18 bits, and the four runs are merged by the same keys."""
+    pts, group, grid = _crowd()
+    mesh = NativeTileMesh(LocationHash2D(**grid), (2, 2), 1)
+    single = Simulation(LocationHash2D(**grid))
+    for t in (mesh, single):
+        _add_crossing(t, pts, group)
+        for _ in range(40):
+            t.step(0.05)
+    rec = single.read_agents()
+    assert rec.tobytes() == mesh.read_agents().tobytes()
+    legs = many_legs(rec, grid)
+    left = thin(single, rec, 7)
+    assert thin(mesh, rec, 7).tobytes() == left.tobytes() and 250 <= len(left) <= 350
+    counts = mesh.tile_counts().reshape(-1)
+    assert (counts > 0).all() and int(counts.sum()) == len(left)
+    want = long_listing_alone(left, grid, legs, 0.5, 2.0, "2 x 2 tiles")
+    check_long_listing(single, left, grid, legs, 0.5, 2.0, "the engine", want)
+    check_long_listing(mesh, left, grid, legs, 0.5, 2.0, "2 x 2 tiles", want)
+    assert mesh.read_agents().tobytes() == left.tobytes()
 
 
 def _two_rank_legs(rec, grid):

@@ -2,7 +2,8 @@
 tests/test_gpu_queries_odd_grids.py: tiles with a non-zero origin on grids far longer than wide, of two-launch size, and
 with a cell size whose multiples are inexact.  For every query family the mesh equals the single engine equals the numpy
 restatement on the engine's OWN read_agents(), byte for byte (the raster's velocity sums within
-field_reference.tolerance), at distances up to halo_cells * cell_size, where a mesh sees across a cut.
+field_reference.tolerance), at distances up to halo_cells * cell_size, where a mesh sees across a cut; the rays and the
+two leg calls (cs_mesh_leg_conflicts, cs_mesh_leg_intervals) have no such limit.
 
 A mesh takes no tile thinner than two halo rings along EITHER axis, cut or not, so the one-cell corridor and strip are
 refused (asserted below); their place is taken by the nearest grids it accepts, two cells wide: 2 x 2,000,003 in
@@ -59,6 +60,11 @@ def test_a_mesh_answers_every_call_as_one_engine(name, shape, halo, scale, monke
         cast = og.ask_rays(single, sc, rec, f"{what} (engine)", scale, longest)
         og.ask_rays(mesh, sc, rec, f"{what} (mesh)", scale, longest, floors=False, want=[h for _, h in cast],
                     rays=[r for r, _ in cast])
+        # the two leg calls: a tile walks only the cells it owns, from its own origin; the legs stay in world coordinates
+        hits = og.ask_legs(single, sc, rec, f"{what} (engine)")
+        og.ask_legs(mesh, sc, rec, f"{what} (mesh)", want=hits)
+        rows = og.ask_intervals(single, sc, rec, f"{what} (engine)")
+        og.ask_intervals(mesh, sc, rec, f"{what} (mesh)", want=rows)
         assert rec.tobytes() == mesh.read_agents().tobytes() == single.read_agents().tobytes()
         for t, who in ((single, "engine"), (mesh, "mesh")):  # (last: the agents of the high quadrant leave both)
             og.ask_by_id(t, rec, w["id"][::-1], f"{what} ({who})")
