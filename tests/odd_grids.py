@@ -65,13 +65,13 @@ def _one_sided(name, nx, ny):
     return Scene(name, _grid(nx, ny), [(walkers[0], fast), (walkers[1], slow)], at_end=("column" if along_x else "row", "cells"))
 
 
-def _lattice(origin):
+def _lattice(origin, n=2025, files=45, seed=3):
     """2,025 agents 0.5 m apart, each moved by up to 0.125 m: 22.5 m x 22.5 m from `origin`; nothing dyadic.  Everybody
     walks along y, in files; every other file is slower and drifts 1.5 cm a second towards its neighbour, so that the model
     turns it aside (walkers of one file keep their distance: crossing files meet within the model's collision distance
-    and the step gives NaN)."""
-    pts = scenes.jittered_lattice(2025, 0.5, origin, 0.25, 3, columns=45)
-    even = (np.arange(len(pts)) % 45) % 2 == 0
+    and the step gives NaN).  n, files: another size, `files` files side by side along x, n / files walkers in each."""
+    pts = scenes.jittered_lattice(n, 0.5, origin, 0.25, seed, columns=files)
+    even = (np.arange(len(pts)) % files) % 2 == 0
     return [(pts[even], (0.0, WALK)), (pts[~even], (0.015, 0.8 * WALK))]
 
 
@@ -103,6 +103,22 @@ def scene(name):
         # (the lattice ends 5 m from the high corner)
         s = Scene(name, grid, _lattice((3.0e6 + 700 * 2.3 - 27.5, -2.0e6 + 900 * 2.3 - 27.5)), eyesight=0.7, at_end=("cells",))
         assert (s.rows, s.cols) == (700, 900)
+        return s
+    if name in ("lopsided", "diagonal"):  # 172 columns x 118 rows of 0.7 m: even 2 x 2 cuts at row 59 and column 86
+        ox, oy = -1234.5, 6789.25
+        grid = dict(width=121.0, height=83.0, cell_size=0.7, offset=(ox, oy))
+        if name == "lopsided":
+            # three lattices in an L, the corner of the L in the low quadrant: 1,800 agents over rows 8-40 and columns
+            # 10-38, 900 over the same rows and columns 100-114, 400 over rows 70-84 and columns 10-24; nobody in the high
+            # quadrant.  The row and the column that halve the crowd both pass through the largest lattice.
+            parts = _lattice((ox + 5.6, oy + 7.0), 1800, 45, 3) + _lattice((ox + 5.6, oy + 70.0), 900, 45, 4) + \
+                _lattice((ox + 49.0, oy + 7.0), 400, 20, 5)
+        else:
+            # two lattices of 1,000 on the diagonal: rows 8-36 and columns 10-27, rows 70-98 and columns 110-127.  Two tiles
+            # of a 2 x 2 mesh hold nobody, with even cuts and with the crowd's own (right behind the first lattice)
+            parts = _lattice((ox + 5.6, oy + 7.0), 1000, 40, 3) + _lattice((ox + 49.0, oy + 77.0), 1000, 40, 4)
+        s = Scene(name, grid, parts, eyesight=0.7, at_end=())
+        assert (s.rows, s.cols) == (118, 172)
         return s
     raise KeyError(name)
 
@@ -242,7 +258,7 @@ def ask_long_axis_rays(sim, sc, rec, name, radius=0.2):
 # May a leg be asked at speed_max = +inf (or distance = +inf)?  Its reach is then without bound and its wave visits every
 # row of the grid one after the other: the two-million-row corridors are not walked whole.
 WHOLE_WALK = {"corridor": False, "corridor2": False, "strip": True, "strip2": True, "tall5": True, "two-launch": True,
-              "odd-cell": True, "odd-far": True, "corner 64": True, f"corner {BIG}": True}
+              "odd-cell": True, "odd-far": True, "lopsided": True, "diagonal": True, "corner 64": True, f"corner {BIG}": True}
 # k_leg_intervals takes the columns of a row as one run of slots, k_leg_conflicts 16 columns at a time: without a reach it
 # looks at 4,097 x 257 = 1.05M chunks of the two-launch grid, one after the other, and at 46,340 x 2,897 = 134M of the
 # 31-bit grid, whatever the number of legs (a leg is a wave): with it the corner test took 114 s on an MI355X, 9 s
@@ -698,15 +714,21 @@ def cuts_of(rects):
     return sorted(set(r[:, 0].tolist()) - {0}), sorted(set(r[:, 2].tolist()) - {0})
 
 
-def astride_cuts(sc, rec, rects):
+def astride_cuts(sc, rec, rects, apart=False):
     """Records of four agents with new positions astride every cut: 0.3 and 0.1 cell either side of it, in the middle of
-    the grid's other axis"""
+    the grid's other axis.  apart: for a crowd that is stepped afterwards: a quarter of a cell either side, two and two
+    0.6 cell apart along the cut, 3 cells from the middle of the other axis (the agents astride a row cut and a column cut
+    that cross in the middle of the grid do not meet); no two are closer than 0.5 cell, 0.35 m where a cell is 0.7 m, and
+    the walking speeds of a scene differ by 0.08 m/s: they stay outside the model's collision distance of 0.2 m for 15
+    steps.  (They keep their velocities: a few standers would be all that the speed filters of the scenes admit.)"""
     cut_rows, cut_cols = cuts_of(rects)
     ox, oy = sc.grid["offset"]
     spots = []
-    for j, f in enumerate((-0.3, -0.1, 0.1, 0.3)):
-        spots += [(ox + (c + f) * sc.cell, oy + (sc.cols // 2 + 0.4 + 0.05 * j) * sc.cell) for c in cut_rows]
-        spots += [(ox + (sc.rows // 2 + 0.4 + 0.05 * j) * sc.cell, oy + (c + f) * sc.cell) for c in cut_cols]
+    places = [(-0.25, 3.0), (0.25, 3.0), (-0.25, 3.6), (0.25, 3.6)] if apart else \
+        [(f, 0.05 * j) for j, f in enumerate((-0.3, -0.1, 0.1, 0.3))]
+    for f, along in places:
+        spots += [(ox + (c + f) * sc.cell, oy + (sc.cols // 2 + 0.4 + along) * sc.cell) for c in cut_rows]
+        spots += [(ox + (sc.rows // 2 + 0.4 + along) * sc.cell, oy + (c + f) * sc.cell) for c in cut_cols]
     part = _sorted(rec[pairs_ref.takes_part(rec, sc.grid)])
     w = part[np.linspace(3, len(part) - 4, len(spots)).astype(np.int64)].copy()
     w["x"], w["y"] = [p[0] for p in spots], [p[1] for p in spots]
@@ -726,3 +748,137 @@ def cut_floor(sc, rec, rects, distance):
           f"{across} across them")
     assert len(across) > 0 and all(n > 0 for n in across)
 
+
+# ---- cuts placed at will, cuts of the crowd, and the floors of the scenes made for them ---------------------------------
+def placed_cut_weights(sc, shape, rows=(), cols=(), halo=1):
+    """Weight points (for NativeTileMesh(weights=) / TileLayout(weights=)) that put the interior edges of a
+    shape[0] x shape[1] mesh at the rows `rows` and the columns `cols`.  _weighted_edges / mesh_weighted_edges put edge k
+    at the first index whose cumulative weight reaches k parts of the total: all the weight of part k in the single row
+    r puts that edge at r + 1, so part k stands in row rows[k] - 1 (the last part in the last row).  A point weighs on
+    both axes, hence one point for every pair (part along x, part along y); the sums are whole numbers, exact in f64.
+    The edges asked for lie at least two halo rings apart (closer ones are pushed apart, and these would not be met)."""
+    assert len(rows) == shape[0] - 1 and len(cols) == shape[1] - 1
+    for edges, n in ((list(rows), sc.rows), (list(cols), sc.cols)):
+        e = [0] + edges + [n]
+        assert all(b - a >= 2 * halo for a, b in zip(e, e[1:])), (e, halo)
+    ox, oy = sc.grid["offset"]
+    in_rows, in_cols = [r - 1 for r in rows] + [sc.rows - 1], [c - 1 for c in cols] + [sc.cols - 1]
+    return np.array([(ox + (r + 0.5) * sc.cell, oy + (c + 0.5) * sc.cell) for r in in_rows for c in in_cols])
+
+
+def rects_of(edges_x, edges_y):
+    """tile_rects() of an in-process mesh with these edges: (x0, x1, y0, y1) per tile, tile tx * tiles_y + ty"""
+    return np.array([(edges_x[i], edges_x[i + 1], edges_y[j], edges_y[j + 1])
+                     for i in range(len(edges_x) - 1) for j in range(len(edges_y) - 1)], dtype=np.uint32)
+
+
+def layout(sc, shape, halo=1, points=None, rec=None):
+    """tiles.TileLayout of the scene's grid, on the CPU: even cuts, the cuts of weights= `points`, or (rec) the cuts
+    cs_mesh_recut makes: the quantiles of numpy histograms of the records' rows and columns (cells_of; agents inside
+    the grid), no tile thinner than two halo rings."""
+    from rmf_crowdsim_amd import LocationHash2D
+    from rmf_crowdsim_amd.tiles import TileLayout
+    index = LocationHash2D(**sc.grid)
+    if rec is not None:
+        row, col = sc.cells_of(rec)
+        assert (row >= 0).all() and (row < sc.rows).all() and (col >= 0).all() and (col < sc.cols).all()
+        hist = (np.bincount(row, minlength=sc.rows), np.bincount(col, minlength=sc.cols))
+        return TileLayout(index, shape[0], shape[1], min_cells=2 * halo, histograms=hist)
+    return TileLayout(index, shape[0], shape[1], weights=points, min_cells=2 * halo)
+
+
+def owners(rects, sc, rec):
+    """the tile (an index into rects) that owns every record"""
+    row, col = sc.cells_of(rec)
+    r = np.asarray(rects, dtype=np.int64)
+    inside = (row[:, None] >= r[:, 0]) & (row[:, None] < r[:, 1]) & (col[:, None] >= r[:, 2]) & (col[:, None] < r[:, 3])
+    assert (inside.sum(axis=1) == 1).all()
+    return inside.argmax(axis=1)
+
+
+def recut_floors(sc, rec, shape=(2, 2), halo=1, empty_before=1, empty_after=0, least=100, moved=8):
+    """The floors of a scene made for a re-cut, by TileLayout and numpy alone (no GPU): with even cuts `empty_before` tiles
+    hold nobody; after the cuts of the crowd `empty_after` do and every other tile holds at least `least` agents; every
+    interior edge moves by at least `moved` cells; no tile is square, before or after.  rec: records, or points (n x 2).
+    -> (rects with even cuts, rects after the re-cut, agents per tile after it)"""
+    if rec.dtype.names is None:
+        pts, rec = rec, np.zeros(len(rec), dtype=[("x", "f8"), ("y", "f8")])
+        rec["x"], rec["y"] = pts[:, 0], pts[:, 1]
+    even, cut = layout(sc, shape, halo), layout(sc, shape, halo, rec=rec)
+    before, after = rects_of(even.x_edges, even.y_edges), rects_of(cut.x_edges, cut.y_edges)
+    n_before = np.bincount(owners(before, sc, rec), minlength=len(before))
+    n_after = np.bincount(owners(after, sc, rec), minlength=len(after))
+    shifts = [abs(a - b) for a, b in zip(even.x_edges[1:-1] + even.y_edges[1:-1], cut.x_edges[1:-1] + cut.y_edges[1:-1])]
+    print(f"{sc.name}: even cuts {even.x_edges} x {even.y_edges} hold {n_before.tolist()}, the crowd's cuts {cut.x_edges} x "
+          f"{cut.y_edges} hold {n_after.tolist()}; the edges move by {shifts} cells")
+    assert int((n_before == 0).sum()) == empty_before and int((n_after == 0).sum()) == empty_after
+    assert (n_after[n_after > 0] >= least).all() and n_after.sum() == len(rec)
+    assert len(shifts) > 0 and min(shifts) >= moved
+    for r in np.concatenate([before, after]).astype(np.int64):
+        assert r[1] - r[0] != r[3] - r[2], r
+    return before, after, n_after
+
+
+def thin_tile_floors(sc, rec, rects, k, halo):
+    """Tile k of `rects` is exactly two halo rings thick between two neighbours: it owns at least 30 agents, pairs within
+    halo * cell exist across BOTH its cuts (cut_floor), and at least one of its agents stands in a cell that the band test
+    of the distance queries at that distance (reach = halo + 1 cells from an edge) puts into the bands of both neighbours.
+    (No agent can be in a PAIR across both cuts: its partners would be 2 * halo cells apart and each closer than halo.)"""
+    r = np.asarray(rects, dtype=np.int64)[k]
+    axis = 0 if r[1] - r[0] == 2 * halo else 1
+    lo, hi = int(r[2 * axis]), int(r[2 * axis + 1])
+    assert hi - lo == 2 * halo and lo > 0 and hi < (sc.rows, sc.cols)[axis]
+    own = owners(rects, sc, rec) == k
+    at = sc.cells_of(rec)[axis][own]
+    both = int(((at < lo + halo + 1) & (at + halo + 1 >= hi)).sum())
+    print(f"{sc.name}: the thin tile {r.tolist()} owns {int(own.sum())} agents, {both} of them in the bands of both neighbours")
+    assert own.sum() >= 30 and both >= 1
+    cut_floor(sc, rec, rects, halo * sc.cell)
+
+
+# ---- one body for "mesh == engine == restatement" -------------------------------------------------------------------------
+FAMILIES = ("select", "field", "near", "encounters", "rays", "legs", "intervals")
+
+
+def ask_mesh_as_engine(mesh, single, sc, rec, what, halo, scale, monkeypatch, longest=INF, cells=None, by_id=None,
+                       removal=True, families=FAMILIES, roles=True):
+    """Every between-step call on a mesh and on its single-engine twin, which hold the records `rec`: each answer is the
+    restatement's on `rec`, which runs once (whoever is asked second is asked with want=).  Selections, rasters and the
+    distance queries at `cells` (None: those of CELLS up to the halo, where a mesh sees across a cut), encounters at a
+    range of halo * cell, the rays, both leg calls; nothing asked has changed a record; then the agents `by_id` are read
+    by id, and (removal) the agents of the high quadrant leave both.  families: a subset, where a test asks less.  One
+    of mesh and single may be None (the ranks of a distributed mesh and their parent hold one each)."""
+    twins = [(t, who) for t, who in ((single, "engine"), (mesh, "mesh")) if t is not None]
+    for t, _ in twins:
+        assert rec.tobytes() == t.read_agents().tobytes(), what
+    limit = halo * sc.cell
+    cells = [c for c in CELLS if c <= halo] if cells is None else list(cells)
+    assert 1.0 in cells  # (one distance IS the limit where the halo is one cell)
+    lhs = {}
+    for t, who in twins:
+        if "select" in families:
+            ask_selections(t, sc, rec, f"{what} ({who})")
+        if "field" in families:
+            ask_fields(t, sc, rec, f"{what} ({who})", monkeypatch)
+        if "near" in families:
+            ask_distance_queries(t, sc, rec, f"{what} ({who})", cells=cells, roles=roles, cache=lhs)
+    rows = cast = hits = spans = None
+    for t, who in twins:
+        if "encounters" in families:
+            rows = ask_encounters(t, sc, rec, f"{what} ({who})", scale, range_=limit, want=rows)
+        if "rays" in families:
+            cast = ask_rays(t, sc, rec, f"{what} ({who})", scale, longest, floors=cast is None,
+                            want=None if cast is None else [h for _, h in cast], rays=None if cast is None else [r for r, _ in cast])
+        # the two leg calls: a tile walks only the cells it owns, from its own origin; the legs stay in world coordinates
+        if "legs" in families:
+            hits = ask_legs(t, sc, rec, f"{what} ({who})", want=hits)
+        if "intervals" in families:
+            spans = ask_intervals(t, sc, rec, f"{what} ({who})", want=spans)
+    for t, who in twins:
+        assert rec.tobytes() == t.read_agents().tobytes(), what
+    for t, who in twins:  # (last: the agents of the high quadrant leave both)
+        if by_id is not None:
+            ask_by_id(t, rec, by_id, f"{what} ({who})")
+        if removal:
+            ask_removal(t, sc, rec, f"{what} ({who})")
+    assert len({t.read_agents().tobytes() for t, _ in twins}) == 1, what

@@ -46,27 +46,6 @@ def test_a_mesh_answers_every_call_as_one_engine(name, shape, halo, scale, monke
         assert int((mesh.tile_counts() > 0).sum()) >= 2
         limit = halo * sc.cell
         og.cut_floor(sc, rec, rects, limit)
-        what = f"{name} in {shape[0]} x {shape[1]} tiles"
-        cells = [c for c in og.CELLS if c <= halo]
-        assert 1.0 in cells  # (one distance IS the limit where the halo is one cell)
-        lhs = {}
-        for t, who in ((single, "engine"), (mesh, "mesh")):
-            og.ask_selections(t, sc, rec, f"{what} ({who})")
-            og.ask_fields(t, sc, rec, f"{what} ({who})", monkeypatch)
-            og.ask_distance_queries(t, sc, rec, f"{what} ({who})", cells=cells, cache=lhs)
-        rows = og.ask_encounters(single, sc, rec, f"{what} (engine)", scale, range_=limit)
-        og.ask_encounters(mesh, sc, rec, f"{what} (mesh)", scale, range_=limit, want=rows)
-        longest = 1000.0 if name == "corridor2" else og.INF
-        cast = og.ask_rays(single, sc, rec, f"{what} (engine)", scale, longest)
-        og.ask_rays(mesh, sc, rec, f"{what} (mesh)", scale, longest, floors=False, want=[h for _, h in cast],
-                    rays=[r for r, _ in cast])
-        # the two leg calls: a tile walks only the cells it owns, from its own origin; the legs stay in world coordinates
-        hits = og.ask_legs(single, sc, rec, f"{what} (engine)")
-        og.ask_legs(mesh, sc, rec, f"{what} (mesh)", want=hits)
-        rows = og.ask_intervals(single, sc, rec, f"{what} (engine)")
-        og.ask_intervals(mesh, sc, rec, f"{what} (mesh)", want=rows)
-        assert rec.tobytes() == mesh.read_agents().tobytes() == single.read_agents().tobytes()
-        for t, who in ((single, "engine"), (mesh, "mesh")):  # (last: the agents of the high quadrant leave both)
-            og.ask_by_id(t, rec, w["id"][::-1], f"{what} ({who})")
-            og.ask_removal(t, sc, rec, f"{what} ({who})")
-        assert mesh.read_agents().tobytes() == single.read_agents().tobytes()
+        # (every family, the by-id reads and at the end the removal: odd_grids.ask_mesh_as_engine)
+        og.ask_mesh_as_engine(mesh, single, sc, rec, f"{name} in {shape[0]} x {shape[1]} tiles", halo, scale, monkeypatch,
+                              longest=1000.0 if name == "corridor2" else og.INF, by_id=w["id"][::-1])
