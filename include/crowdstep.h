@@ -264,7 +264,11 @@ uint32_t cs_register_hlp(cs_engine*, const cs_hlp_desc*); /* highlevel_planners.
 int cs_add_agents(cs_engine*, const double* xy, size_t n, uint32_t hlp,
                   uint32_t lp, double eyesight, uint64_t* out_ids);
 /* Simulation::remove_agents (unknown id: returns Err instead of panicking)
- *                                                               lib.rs:176-192 */
+ *                                                               lib.rs:176-192
+ * 0 = removed, 2 = "unknown agent id": nobody here has this id (on a tile engine another tile may).
+ * On a tile engine whose arrays hold ghosts (between cs_halo_unpack* or a ghost spawn and the step)
+ * only an owned agent is removed: an id that only a ghost holds is answered with 2 and nothing is
+ * killed, so a host that asks its tiles in turn removes the agent from its owner. */
 int cs_remove_agent(cs_engine*, uint64_t id);
 /* Simulation::add_source_sink / remove_source_sink              lib.rs:159-168
  * Returns the handle, or UINT32_MAX (cs_last_error says why).  On a tile engine the first leg of a
@@ -289,7 +293,11 @@ int cs_synchronize(cs_engine*);
 
 /* ---- observation ------------------------------------------------------- */
 size_t cs_agent_count(cs_engine*);                       /* agents.len(), lib.rs:71 */
-/* `pub agents` view, ascending id; returns number written       lib.rs:71    */
+/* `pub agents` view, ascending id; returns number written       lib.rs:71
+ * On a tile engine both speak of the agents the tile owns.  While its arrays hold ghosts (between
+ * cs_halo_unpack* or a ghost spawn and the step) those are the live records in its owned cells:
+ * cs_agent_count counts them and cs_read_agents lists them and no ghost, so the lists of the tiles
+ * of a mesh put together name every agent once (the rule of the calls of crowdstep_state.h). */
 size_t cs_read_agents(cs_engine*, cs_agent_view* out, size_t cap);
 size_t cs_drain_events(cs_engine*, cs_event* out, size_t cap);
 /* Events are queued only while recording is on (default on).  A host without listeners

@@ -309,7 +309,8 @@ int cs_add_agents(cs_engine* e, const double* xy, size_t n, uint32_t hlp, uint32
 }
 
 // Simulation::remove_agents, lib.rs:176-192.  0 = removed, 2 = nobody here has this id (on a tile:
-// another tile may), anything else = the engine's own failure (poisoned, HIP error).
+// another tile may), anything else = the engine's own failure (poisoned, HIP error).  A tile whose arrays hold
+// ghosts removes only an agent it owns: an id that only a ghost holds is "nobody here".
 int cs_remove_agent(cs_engine* e, uint64_t id) {
   hipSetDevice(e->device);
   e->halo_invalidate();  // also where the agent is not found: every tile is asked, all must agree on what follows
@@ -336,8 +337,9 @@ int cs_remove_agent(cs_engine* e, uint64_t id) {
       return 90;
     }
     bool ok = hipMemcpyAsync(e->find_dev, found, sizeof found, hipMemcpyHostToDevice, e->stream) == hipSuccess;
-    hipLaunchKernelGGL(k_remove_by_id, dim3((e->n_slots + 255u) / 256u), dim3(256), 0, e->stream, e->buf[e->cur],
-                       e->n_slots, e->ctr, e->gdev.tile, (uint32_t)dev, e->find_dev);
+    hipLaunchKernelGGL(k_remove_by_id, dim3((e->n_slots + 255u) / 256u), dim3(256), 0, e->stream, e->gdev, e->buf[e->cur],
+                       e->n_slots, e->ctr, e->gdev.tile, (e->tile && e->ghosts_present) ? 1u : 0u, (uint32_t)dev,
+                       e->find_dev);
     ok = ok && hipMemcpyAsync(found, e->find_dev, sizeof found, hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
          hipStreamSynchronize(e->stream) == hipSuccess;
     if (!ok) {
@@ -469,6 +471,22 @@ int cs_synchronize(cs_engine* e) {
 size_t cs_agent_count(cs_engine* e) {
   hipSetDevice(e->device);
   e->refresh_counts();
+  if (e->tile && e->ghosts_present && e->n_slots) {
+    // The host's count is the number of agents the last step moved.  Since then the exchange has handed over those that
+    // walked across a cut and brought ghosts: the agents of this tile are the live records in its owned cells, the ones
+    // cs_read_agents lists and the selections count.
+    uint32_t owned = 0;
+    bool ok = e->find_dev || hipMalloc(&e->find_dev, 2 * sizeof(uint32_t)) == hipSuccess;
+    ok = ok && hipMemsetAsync(e->find_dev, 0, sizeof(uint32_t), e->stream) == hipSuccess;
+    if (ok)
+      hipLaunchKernelGGL(k_tile_count_owned, dim3((e->n_slots + 255u) / 256u), dim3(256), 0, e->stream, e->gdev,
+                         e->buf[e->cur], e->n_slots, e->ctr, e->find_dev);
+    ok = ok && hipMemcpyAsync(&owned, e->find_dev, sizeof owned, hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
+         hipStreamSynchronize(e->stream) == hipSuccess;
+    if (ok) return (size_t)owned + e->limbo.size();
+    // (the call has no way to fail: cs_last_error says that what follows is the count of the last step)
+    e->error = "HIP error while counting the agents of a tile that holds ghosts";
+  }
   return (size_t)e->n_alive_host + e->limbo.size();
 }
 
@@ -477,9 +495,25 @@ size_t cs_read_agents(cs_engine* e, cs_agent_view* out, size_t cap) {
   if (e->refresh_counts() != 0) return 0;
   cs_engine::HostState h;
   if (e->download(&h) != 0) return 0;
+  // A tile whose arrays hold ghosts lists the agents it owns (what cs_agent_count counts, the rule of k_tile_export):
+  // n_slots is then an upper bound, the records in use end at the device's n_pending.
+  const bool owned_only = e->tile && e->ghosts_present;
+  uint32_t in_use = e->n_slots;
+  if (owned_only) {
+    Counters c;
+    if (e->read_counters(&c) != 0) return 0;
+    in_use = std::min(in_use, c.n_pending);
+  }
+  const GridDev& g = e->gdev;
   std::vector<uint32_t> live;
-  for (uint32_t i = 0; i < e->n_slots; ++i)
-    if (h.cell[i] != CS_INVALID_CELL) live.push_back(i);
+  for (uint32_t i = 0; i < in_use; ++i) {
+    if (h.cell[i] == CS_INVALID_CELL) continue;
+    if (owned_only) {
+      const uint32_t cx = h.cell[i] / g.nx, cy = h.cell[i] - cx * g.nx;
+      if (cx < g.own_x0 || cx >= g.own_x1 || cy < g.own_y0 || cy >= g.own_y1) continue;  // a ghost
+    }
+    live.push_back(i);
+  }
   std::sort(live.begin(), live.end(), [&](uint32_t a, uint32_t b) { return h.id[a] < h.id[b]; });
   size_t n = std::min(cap, live.size());
   for (size_t k = 0; k < n; ++k) {

@@ -427,6 +427,22 @@ __global__ void k_tile_histogram(GridDev g, AgentArrays a, uint32_t n_ub, const 
   atomicAdd(&rows[g.org_x + cx], 1u);
   atomicAdd(&cols[g.org_y + cy], 1u);
 }
+// The live records in the owned cells of a tile whose arrays hold ghosts: what cs_agent_count reports in that state (the
+// host's count is the number of agents the last step moved; the exchange has handed some over since).  One atomic per wave.
+__global__ void k_tile_count_owned(GridDev g, AgentArrays a, uint32_t n_ub, const Counters* __restrict__ ctr,
+                                   uint32_t* __restrict__ count) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool mine = false;
+  if (i < n_ub && i < ctr->n_pending) {
+    const uint32_t c = a.cell[i];
+    if (c != CS_INVALID_CELL) {
+      const uint32_t cx = c / g.nx, cy = c - cx * g.nx;
+      mine = cx >= g.own_x0 && cx < g.own_x1 && cy >= g.own_y0 && cy < g.own_y1;
+    }
+  }
+  const unsigned long long m = __ballot(mine);
+  if (m && __lane_id() == __ffsll((long long)m) - 1) atomicAdd(count, (uint32_t)__popcll(m));
+}
 __global__ void k_tile_export(GridDev g, AgentArrays a, uint32_t n_ub, const Counters* __restrict__ ctr,
                               uint32_t owned_only, HaloRecord* __restrict__ out, uint32_t cap,
                               uint32_t* __restrict__ count) {
@@ -596,13 +612,19 @@ __global__ void k_repack_meta(uint32_t* __restrict__ meta, uint32_t n, uint32_t 
   meta[i] = (m & ((1u << from_bits) - 1u)) | ((m >> from_bits) << to_bits);
 }
 
-// found[0] = slot (or 0xFFFFFFFF), found[1] = its meta word.
+// found[0] = slot (or 0xFFFFFFFF), found[1] = its meta word.  `owned_only`: a tile whose arrays hold ghosts removes only
+// an agent in its owned cells (the rule of k_write_match): the ghost copy of a neighbour's agent is nobody here.
 // ---------------------------------------------------------------------------
-__global__ void k_remove_by_id(AgentArrays a, uint32_t n_ub, const Counters* __restrict__ ctr, uint32_t tile,
-                               uint32_t id, uint32_t* __restrict__ found) {
+__global__ void k_remove_by_id(GridDev g, AgentArrays a, uint32_t n_ub, const Counters* __restrict__ ctr, uint32_t tile,
+                               uint32_t owned_only, uint32_t id, uint32_t* __restrict__ found) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_ub || (tile && i >= ctr->n_pending)) return;
-  if (a.cell[i] == CS_INVALID_CELL || a.id[i] != id) return;
+  const uint32_t c = a.cell[i];
+  if (c == CS_INVALID_CELL || a.id[i] != id) return;
+  if (owned_only) {
+    const uint32_t cx = c / g.nx, cy = c - cx * g.nx;
+    if (cx < g.own_x0 || cx >= g.own_x1 || cy < g.own_y0 || cy >= g.own_y1) return;  // a ghost
+  }
   found[0] = i;
   found[1] = a.meta[i];
   a.cell[i] = CS_INVALID_CELL;

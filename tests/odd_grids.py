@@ -882,3 +882,424 @@ def ask_mesh_as_engine(mesh, single, sc, rec, what, halo, scale, monkeypatch, lo
         if removal:
             ask_removal(t, sc, rec, f"{what} ({who})")
     assert len({t.read_agents().tobytes() for t, _ in twins}) == 1, what
+
+
+# ---- tile engines that hold ghosts: between a halo unpack and the step (tests/test_gpu_queries_ghost_tiles.py) -------------
+def populate_kept(sc, sim):
+    """Scene.populate that keeps what a selection by owner needs -> [(high-level planner, the ids of its agents)]"""
+    out = []
+    for pts, vel in sc.parts:
+        hlp = StubHighLevelPlan(vel)
+        out.append((hlp, np.asarray(sim.add_agents(np.asarray(pts), hlp, LP, sc.eyesight), dtype=np.uint64)))
+    return out
+
+
+def ghost_twins(sc, shape, halo, weights=None, phases=1, flags=0, steps=STEPS, meshes=1):
+    """`meshes` LocalTileMesh (the Python mesh, whose exchange a test can make by hand) and a single engine, populated
+    and stepped alike -> ([mesh, ...], single, [(planner, ids)] of the first mesh)"""
+    from rmf_crowdsim_amd import LocationHash2D, Simulation
+    from rmf_crowdsim_amd.tiles import LocalTileMesh
+    twins = [LocalTileMesh(LocationHash2D(**sc.grid), shape, halo, weights=weights, phases=phases, flags=flags)
+             for _ in range(meshes)] + [Simulation(LocationHash2D(**sc.grid), flags=flags)]
+    kept = [populate_kept(sc, t) for t in twins]
+    for _ in range(steps):
+        for t in twins:
+            t.step(DT)
+    return twins[:-1], twins[-1], kept[0]
+
+
+def unpack_ghosts(mesh):
+    """The first half of LocalTileMesh.step: pack, move the buffers, unpack.  Every engine holds its ghost ring."""
+    if mesh.phases == 2:
+        mesh._exchange(0)
+        mesh._exchange(1)
+    else:
+        mesh._exchange_all()
+
+
+def finish_step(mesh, dt=DT, report=False):
+    """The second half of LocalTileMesh.step for a mesh without source-sinks"""
+    for e in mesh.engines:
+        e.step(dt, report=report)
+
+
+def mesh_rects(mesh):
+    return rects_of(mesh.layout.x_edges, mesh.layout.y_edges)
+
+
+def held_by_tiles(sc, rects, rec, halo):
+    """By numpy alone, per tile of `rects`: (the records it owns, the records its ghost ring holds after an unpack: those
+    whose cell lies in its rectangle grown by `halo` cells, clipped to the grid, but not in the rectangle)"""
+    row, col = sc.cells_of(rec)
+    own = owners(rects, sc, rec)
+    out = []
+    for k, (x0, x1, y0, y1) in enumerate(np.asarray(rects, dtype=np.int64).tolist()):
+        grown = (row >= x0 - halo) & (row < x1 + halo) & (col >= y0 - halo) & (col < y1 + halo)
+        out.append((rec[own == k], rec[grown & (own != k)]))
+    return out
+
+
+def _join(own, ghosts):
+    return _sorted(np.concatenate([own, ghosts]))
+
+
+def _differs(a, b):
+    """do two answers of a restatement differ (arrays, or tuples of arrays)"""
+    a, b = (a if isinstance(a, (tuple, list)) else (a,)), (b if isinstance(b, (tuple, list)) else (b,))
+    return any(np.asarray(p).tobytes() != np.asarray(q).tobytes() for p, q in zip(a, b))
+
+
+def cut_sides(sc, rect):
+    """The sides of a tile's rectangle that are cuts (a neighbour and a ring lie beyond): (axis, the owned row or column
+    next to the cut, the ring row or column next to that)"""
+    x0, x1, y0, y1 = (int(v) for v in rect)
+    sides = []
+    if x0 > 0:
+        sides.append((0, x0, x0 - 1))
+    if x1 < sc.rows:
+        sides.append((0, x1 - 1, x1))
+    if y0 > 0:
+        sides.append((1, y0, y0 - 1))
+    if y1 < sc.cols:
+        sides.append((1, y1 - 1, y1))
+    return sides
+
+
+def ghost_floors(sc, rects, held, halo, distance, least=20, loose=()):
+    """By numpy alone, before any engine is asked: every tile holds at least `least` ghosts; at every side of a tile that
+    is a cut an owned agent stands in the owned row (column) next to it and a ghost in the ring row (column) beyond,
+    the two closer than `distance` (an off-by-one clip of a walk by own_* then changes an answer); on at least one tile
+    own_x0, own_x1, own_y0, own_y1 of the local grid are four different numbers.  loose: the tiles whose sides are only
+    printed (a tile that owns nobody, a tile whose crowd stands far from its cuts)."""
+    four = 0
+    for k, ((own, ghosts), rect) in enumerate(zip(held, np.asarray(rects, dtype=np.int64).tolist())):
+        x0, x1, y0, y1 = rect
+        lx0, ly0 = max(x0 - halo, 0), max(y0 - halo, 0)
+        local = (x0 - lx0, x1 - lx0, y0 - ly0, y1 - ly0)  # own_x0, own_x1, own_y0, own_y1 (cs_engine::set_geometry)
+        four += len(set(local)) == 4
+        sides = []
+        for axis, inner, outer in cut_sides(sc, rect):
+            a = own[sc.cells_of(own)[axis] == inner]
+            g = ghosts[sc.cells_of(ghosts)[axis] == outer]
+            near = 0
+            if len(a) and len(g):
+                d2 = (a["x"][:, None] - g["x"][None, :]) ** 2 + (a["y"][:, None] - g["y"][None, :]) ** 2
+                near = int((d2 < distance * distance).sum())
+            sides.append((("row", "column")[axis], inner, len(a), len(g), near))
+        print(f"{sc.name}: tile {k} {rect} (own_* {local}) owns {len(own)} agents and holds {len(ghosts)} ghosts; "
+              f"(axis, owned line, agents in it, ghosts beyond, pairs within {distance:.2f} m): {sides}")
+        assert len(ghosts) >= least, (k, len(ghosts))
+        assert k in loose or all(s[2] > 0 and s[3] > 0 and s[4] > 0 for s in sides), (k, sides)
+    assert four >= 1
+    return held
+
+
+def ghost_selections(sc, rect, own, ghosts, halo, handle_of):
+    """Selections that straddle the cuts of a tile: its rectangle grown by halo + 1 cells; a box of 6 x 6 cells round a
+    ghost; a circle of 2.5 cells round another; the speeds of the half of the crowd (slower or faster) a ghost belongs
+    to; the planner of a ghost.  handle_of(agent id) -> the handle of its high-level planner."""
+    ox, oy = sc.grid["offset"]
+    cell = sc.cell
+    x0, x1, y0, y1 = (int(v) for v in rect)
+    g, h = ghosts[0], ghosts[len(ghosts) // 2]
+    both = _join(own, ghosts)
+    mid = _speeds(both)[1]
+    slow = float(np.hypot(g["vx"], g["vy"])) < mid
+    return [("the tile and two cells round it", selection(_abi.CS_SEL_RECT, x0=ox + (x0 - halo - 1) * cell, y0=oy + (y0 - halo - 1) * cell,
+                                                          x1=ox + (x1 + halo + 1) * cell, y1=oy + (y1 + halo + 1) * cell)),
+            ("a box round a ghost", selection(_abi.CS_SEL_RECT, x0=float(g["x"]) - 3 * cell, y0=float(g["y"]) - 3 * cell,
+                                              x1=float(g["x"]) + 3 * cell, y1=float(g["y"]) + 3 * cell)),
+            ("a circle round a ghost", selection(_abi.CS_SEL_CIRCLE, cx=float(h["x"]), cy=float(h["y"]), r=2.5 * cell)),
+            ("the speed of a ghost", selection(_abi.CS_SEL_SPEED, speed_lo=0.0 if slow else mid, speed_hi=mid if slow else INF)),
+            ("the planner of a ghost", selection(_abi.CS_SEL_HLP, hlp=int(handle_of(int(g["id"])))))]
+
+
+def ghost_rays(sc, rect, own, ghosts, halo):
+    """Rays for a tile that holds ghosts: from 32 ghosts (origins in the ring; without `ignore` each starts inside its
+    ghost) towards the middle of the tile and on to the ring beyond; along the first and the last owned row and column
+    from 3 cells outside the grown rectangle, through ring, tile and ring; the fans and random rays of ray_sets about the
+    tile's own and ghost records."""
+    ox, oy = sc.grid["offset"]
+    cell = sc.cell
+    x0, x1, y0, y1 = (int(v) for v in rect)
+    mid = np.array([ox + 0.5 * (x0 + x1) * cell, oy + 0.5 * (y0 + y1) * cell])
+    g = ghosts[np.linspace(0, len(ghosts) - 1, min(32, len(ghosts))).astype(np.int64)]
+    o = np.column_stack([g["x"], g["y"]])
+    u = mid[None, :] - o
+    u /= np.hypot(u[:, 0], u[:, 1])[:, None]
+    through = rays_ref.rays_array(o, u)
+    lines_o, lines_u = [], []
+    for r in (x0, x1 - 1):
+        for f in (0.25, 0.75):
+            lines_o.append((ox + (r + f) * cell, oy + (y0 - halo - 3) * cell))
+            lines_u.append((0.0, 1.0))
+    for c in (y0, y1 - 1):
+        for f in (0.25, 0.75):
+            lines_o.append((ox + (x0 - halo - 3) * cell, oy + (c + f) * cell))
+            lines_u.append((1.0, 0.0))
+    lines = rays_ref.rays_array(np.array(lines_o), np.array(lines_u))
+    return np.concatenate([through, lines, ray_sets(_join(own, ghosts), sc.grid, 30.0, beams=45, segments=150)])
+
+
+def ghost_legs(sc, rect, own, ghosts, halo, intervals=False):
+    """Legs for a tile that holds ghosts: waits of 1.5 s 0.1 cell beside 32 ghosts; legs of 4 s along the first and the
+    last owned row and column from 2 cells outside the grown rectangle to 2 cells beyond it; the leg sets of the leg
+    tests about the tile's own and ghost records."""
+    ox, oy = sc.grid["offset"]
+    cell = sc.cell
+    x0, x1, y0, y1 = (int(v) for v in rect)
+    g = ghosts[np.linspace(0, len(ghosts) - 1, min(32, len(ghosts))).astype(np.int64)]
+    waits = legs_ref.legs_array(np.column_stack([g["x"] + 0.1 * cell, g["y"]]), (0.0, 0.0), 0.0, 1.5)
+    starts, vels = [], []
+    for r in (x0, x1 - 1):
+        starts.append((ox + (r + 0.5) * cell, oy + (y0 - halo - 2) * cell))
+        vels.append((0.0, (y1 - y0 + 2 * halo + 4) * cell / 4.0))
+    for c in (y0, y1 - 1):
+        starts.append((ox + (x0 - halo - 2) * cell, oy + (c + 0.5) * cell))
+        vels.append(((x1 - x0 + 2 * halo + 4) * cell / 4.0, 0.0))
+    lines = np.concatenate([legs_ref.legs_array(np.array([s]), v, 0.0, 4.0) for s, v in zip(starts, vels)])
+    both = _join(own, ghosts)
+    rest = interval_legs(both, sc.grid, segments=150) if intervals else leg_sets(both, sc.grid, segments=150)
+    return np.concatenate([waits, lines, rest])
+
+
+def ghost_raster(sc, rect, halo):
+    """the tile's rectangle grown by halo + 1 cells, cell by cell: a raster window across every cut of the tile"""
+    ox, oy = sc.grid["offset"]
+    x0, x1, y0, y1 = (int(v) for v in rect)
+    return field_ref.desc(ox + (x0 - halo - 1) * sc.cell, oy + (y0 - halo - 1) * sc.cell, sc.cell, sc.cell,
+                          x1 - x0 + 2 * halo + 2, y1 - y0 + 2 * halo + 2)
+
+
+def ask_tile_with_ghosts(engine, sc, rect, own, ghosts, elsewhere, halo, name, monkeypatch, handle_of):
+    """Every between-step read on ONE tile engine whose arrays hold ghosts: each answer is the restatement's on `own`, the
+    records the tile owns, byte for byte (the raster's sums within field_reference.tolerance).  Before each call the
+    floor that lets it fail, by the restatement alone: its answer on the owned records and the ghosts together differs
+    from its answer on the owned records.  elsewhere: records the tile does not hold at all.  engine None: the floors
+    alone, as tests/test_ghost_tile_floors.py evaluates them without a GPU.  -> the names of the floors met"""
+    grid, cell = sc.grid, sc.cell
+    both = _join(own, ghosts)
+    met = []
+
+    def floor(what, a, b, differ=None):
+        assert _differs(a, b) if differ is None else differ, f"{name}, {what}: the ghosts do not change the restatement's answer"
+        met.append(what)
+        return engine is not None
+
+    # the count and the list
+    if floor("len and read_agents", own, both):
+        assert len(engine) == len(own), name
+        assert engine.read_agents().tobytes() == own.tobytes(), name
+    # selections and counts
+    sels = ghost_selections(sc, rect, own, ghosts, halo, handle_of)
+    hlp_of = lambda rec: np.array([handle_of(int(i)) for i in rec["id"]], dtype=np.uint64)  # noqa: E731
+    wants = []
+    for what, sel in sels:
+        want = own["id"][pred(sel, own, None, hlp_of(own), None)]
+        wants.append(len(want))
+        if not floor(f"select {what}", want, both["id"][pred(sel, both, None, hlp_of(both), None)]):
+            continue
+        n, got = select(engine, sel, cap=len(both) + 3)
+        print(f"{name}, select {what}: restatement {len(want)} of {len(own)} owned, engine {n}")
+        assert n == len(want) and got.tolist() == want.tolist(), (name, what)
+        if len(want) > 3:
+            n, few = select(engine, sel, cap=len(want) // 2)
+            assert n == len(want) and few.tolist() == want[:len(want) // 2].tolist(), (name, what)
+    if engine is not None:
+        rc, counts = count(engine, [s for _, s in sels])
+        assert rc == 0 and counts.tolist() == wants, name
+        s = sels[0][1]
+        assert engine.select_agents(rect=(s.x0, s.y0, s.x1, s.y1)).tolist() == own["id"].tolist(), name
+        assert engine.count_agents([dict(rect=(s.x0, s.y0, s.x1, s.y1))]).tolist() == [len(own)], name
+    # the raster, in the form cs_agent_field picks and in the global form
+    d = ghost_raster(sc, rect, halo)
+    want = field_ref.raster(d, own)
+    if floor("agent_field", want[0], field_ref.raster(d, both)[0]):
+        for limit in (None, "0"):
+            if limit is None:
+                monkeypatch.delenv("CS_FIELD_LDS_BYTES", raising=False)
+            else:
+                monkeypatch.setenv("CS_FIELD_LDS_BYTES", limit)
+            for form in ("count", "both"):
+                rc, cnt, sums = field_ref.field(engine, d, None, want=form)
+                assert rc == 0, (name, field_ref.last_error(engine))
+                field_ref.check(f"{name}, raster, {form}, LDS limit {limit}", cnt, sums, want)
+        monkeypatch.delenv("CS_FIELD_LDS_BYTES", raising=False)
+    # the distance queries, at 0.6 cell and at the halo; once with roles
+    lhs_own, lhs_both = {}, {}
+    half, slow = sels[1][1], sels[0][1]  # the roles: the box round a ghost, which lies across a cut, and the tile and its rings
+    for c in (0.6, float(halo)):
+        dist = c * cell
+        if floor(f"close_pairs {c}", pairs_ref.pairs(own, grid, dist, cache=lhs_own), pairs_ref.pairs(both, grid, dist, cache=lhs_both)):
+            pairs_ref.agree(engine, own, grid, dist, name=f"{name}, pairs, {c} cells", cache=lhs_own)
+        # (where an owned agent stands within the distance of a ghost, the rows of the OWNED subjects must change: a ghost
+        # is somebody's neighbour; elsewhere the ghosts' own rows are the difference)
+        with_ghosts = neighbours_ref.neighbours(both, grid, dist, cache=lhs_both)
+        across, _ = pairs_ref.pairs(both, grid, dist, np.isin(both["id"], own["id"]), np.isin(both["id"], ghosts["id"]),
+                                    cache=lhs_both)
+        if floor(f"agent_neighbours {c}", neighbours_ref.neighbours(own, grid, dist, cache=lhs_own),
+                 with_ghosts[np.isin(with_ghosts["id"], own["id"])] if len(across) else with_ghosts):
+            neighbours_ref.agree(engine, own, grid, dist, name=f"{name}, neighbours, {c} cells", cache=lhs_own, min_counts=(0, 2))
+        if floor(f"agent_clusters {c}", clusters_ref.clusters(own, grid, dist, cache=lhs_own)[:3],
+                 clusters_ref.clusters(both, grid, dist, cache=lhs_both)[:3]):
+            clusters_ref.agree(engine, own, grid, dist, name=f"{name}, clusters, {c} cells", cache=lhs_own)
+    dist = halo * cell
+    if floor("close_pairs, two roles", pairs_ref.pairs(own, grid, dist, *pairs_ref.roles(half, slow, own), cache=lhs_own),
+             pairs_ref.pairs(both, grid, dist, *pairs_ref.roles(half, slow, both), cache=lhs_both)):
+        pairs_ref.agree(engine, own, grid, dist, half, slow, name=f"{name}, pairs, two roles", cache=lhs_own)
+        neighbours_ref.agree(engine, own, grid, dist, half, slow, name=f"{name}, neighbours, two roles", cache=lhs_own)
+        clusters_ref.agree(engine, own, grid, dist, half, min_size=2, name=f"{name}, clusters of one role", cache=lhs_own)
+    # encounters
+    args = (0.5, 3.0, halo * cell)
+    want = encounters_ref.encounters(own, grid, *args)
+    if floor("encounters", want, encounters_ref.encounters(both, grid, *args)):
+        encounters_ref.agree(engine, own, grid, *args, name=f"{name}, encounters", want=want)
+    # rays
+    rays = ghost_rays(sc, rect, own, ghosts, halo)
+    for radius in (0.2, 0.4):
+        want = rays_ref.cast(own, grid, rays, radius)
+        if floor(f"cast_rays {radius}", want, rays_ref.cast(both, grid, rays, radius)):
+            rays_ref.agree(engine, own, grid, rays, radius, name=f"{name}, rays {radius}", want=want)
+    # leg conflicts and leg intervals: everybody slower than 2 m/s within 0.4 cell; the walk without a reach within 0.8 cell
+    for what, ref, restate, legs in (("leg_conflicts", legs_ref, legs_ref.conflicts, ghost_legs(sc, rect, own, ghosts, halo)),
+                                     ("leg_intervals", intervals_ref, intervals_ref.intervals,
+                                      ghost_legs(sc, rect, own, ghosts, halo, intervals=True))):
+        for dist, speed_max in ((0.4 * cell, 2.0), (0.8 * cell, INF)):
+            want = restate(own, grid, legs, dist, speed_max)
+            if floor(f"{what} {speed_max}", want, restate(both, grid, legs, dist, speed_max)):
+                ref.agree(engine, own, grid, legs, dist, speed_max, name=f"{name}, {what} {(dist, speed_max)}", want=want)
+    # the Python surface of the two leg calls: waits beside ghosts, and a path from ring to ring through the tile
+    from rmf_crowdsim_amd.simulation import free_spans, merge_leg_intervals, paths_legs
+    g = ghosts[np.linspace(0, len(ghosts) - 1, min(24, len(ghosts))).astype(np.int64)]
+    spots = np.column_stack([g["x"] + 0.3, g["y"]])
+    waits = legs_ref.legs_array(spots, (0.0, 0.0), 0.5, 4.0)
+
+    def spans(rec):
+        rows, _ = intervals_ref.intervals(rec, grid, waits, 0.3, 2.0)
+        return free_spans(*merge_leg_intervals(rows, len(waits)), waits["t0"], waits["t1"])
+    want = spans(own)
+    if floor("free_intervals", None, None, differ=want != spans(both)):
+        assert engine.free_intervals(spots, 0.5, 4.0, 0.3, 2.0) == want, name
+    # (from the ghost that stands farthest from every owned agent, 5 cm beside it: with ghosts it is the conflict, at once)
+    if len(own):
+        apart = ((ghosts["x"][:, None] - own["x"][None, :]) ** 2 + (ghosts["y"][:, None] - own["y"][None, :]) ** 2).min(axis=1)
+        lone = ghosts[int(np.argmax(apart))]
+    else:
+        lone = ghosts[0]
+    start = np.array([float(lone["x"]) + 0.05, float(lone["y"])])
+    mid = np.array([np.median(both["x"]), np.median(both["y"])])
+    far = np.array([g["x"].max(), g["y"].max()]) + 0.5
+    path = (np.array([start, mid, mid, far]), np.array([0.0, 4.0, 5.0, 9.0]))  # (the second leg is a wait)
+    legs, _ = paths_legs([path])
+
+    def first(rec):
+        hits = legs_ref.conflicts(rec, grid, legs, 0.3, 2.0)
+        at = np.nonzero(hits["id"] != legs_ref.NO_HIT)[0]
+        if not len(at):
+            return None
+        k = int(at[0])
+        l, s = legs[k], float(hits["s"][k])
+        return (int(hits["id"][k]), float(l["t0"]) + s, k, (float(l["x0"]) + float(l["vx"]) * s, float(l["y0"]) + float(l["vy"]) * s))
+    want = first(own)
+    if floor("path_conflict", None, None, differ=want != first(both)):
+        assert engine.path_conflict(*path, 0.3, 2.0) == want, name
+    # reads by id: owned agents, ghosts of this tile, agents the tile does not hold at all
+    some = [r[np.linspace(0, len(r) - 1, min(16, len(r))).astype(np.int64)] for r in (own, ghosts, elsewhere)]
+    ids = np.concatenate([r["id"] for r in some])[::-1].copy()
+    mine = np.isin(ids, own["id"])
+    assert len(some[2]) > 0 or len(elsewhere) == 0
+    if floor("read_agents_by_id", mine, np.isin(ids, both["id"])):
+        out, found = engine.read_agents_by_id(ids, missing_ok=True)
+        assert np.asarray(found, dtype=bool).tolist() == mine.tolist(), name
+        at = {int(i): j for j, i in enumerate(own["id"])}
+        assert out[mine].tobytes() == own[[at[int(i)] for i in ids[mine]]].tobytes(), name
+        blank = np.zeros(int((~mine).sum()), dtype=out.dtype)
+        blank["id"] = ids[~mine]
+        assert out[~mine].tobytes() == blank.tobytes(), name
+        # asking has changed no record and nobody's ownership
+        assert len(engine) == len(own) and engine.read_agents().tobytes() == own.tobytes(), name
+    return met
+
+
+# (scene, shape, halo, phases of the exchange, the rows and the columns of the placed cuts; None: the weights are the
+# crowd's own points, whose cuts pass through the largest lattice of the lopsided crowd).  Row and column 24 pass through
+# that lattice too; the middle tile of the (3, 1) and (1, 3) meshes is two halo rings thick, with a ring on both sides.
+# "diagonal": the row cut through the first lattice, the column cut right behind it: the tile of rows 0-23 beyond column 29
+# owns nobody and holds the last two columns of the lattice as ghosts.  "odd-far": cells of 2.3 m, the cuts through the
+# lattice in the high corner of 700 x 900 cells.
+GHOST_CASES = [("lopsided", (2, 2), 1, 1, None), ("lopsided", (2, 2), 2, 2, None), ("lopsided", (3, 1), 1, 2, ((24, 26), ())),
+               ("lopsided", (3, 1), 2, 1, ((24, 28), ())), ("lopsided", (1, 3), 1, 1, ((), (24, 26))),
+               ("lopsided", (1, 3), 2, 2, ((), (24, 28))), ("diagonal", (2, 2), 2, 1, ((24,), (29,))),
+               ("odd-far", (2, 2), 1, 2, ((693,), (894,)))]
+GHOST_IDS = [f"{s}-{a}x{b}-halo{h}-phases{p}" for s, (a, b), h, p, _ in GHOST_CASES]
+# tiles exempt from the floor of the sides (ghost_floors): on the diagonal scene the column cut lies BEHIND the lattice, so
+# that tile 1 owns nobody: nobody stands beyond it for tiles 0 and 2 (their row sides meet the floor), and tile 3 owns the
+# second lattice, 80 cells from its cuts (its ghosts are a corner of the first).  The floor holds on every tile of every
+# other case.
+GHOST_LOOSE = {"diagonal": (0, 1, 2, 3)}
+
+
+def ghost_case_weights(sc, shape, halo, placed):
+    if placed is None:
+        return np.concatenate([p for p, _ in sc.parts])
+    return placed_cut_weights(sc, shape, placed[0], placed[1], halo)
+
+
+def ghost_case_floors(case, rec):
+    """By TileLayout and numpy alone, for the records `rec` of the scene's crowd after the steps: the rectangles, what every
+    tile owns and holds as ghosts, the floors of ghost_floors -> (sc, rects, held)"""
+    name, shape, halo, _, placed = case
+    sc = scene(name)
+    lay = layout(sc, shape, halo, points=ghost_case_weights(sc, shape, halo, placed))
+    rects = rects_of(lay.x_edges, lay.y_edges)
+    if placed is not None:
+        assert rects.tolist() == rects_of([0, *placed[0], sc.rows], [0, *placed[1], sc.cols]).tolist()
+    assert all(int(r[1]) - int(r[0]) != int(r[3]) - int(r[2]) for r in rects)  # (no tile is square)
+    held = held_by_tiles(sc, rects, rec, halo)
+    ownerless = [k for k, (own, _) in enumerate(held) if len(own) == 0]
+    assert len(ownerless) == (1 if name == "diagonal" else 0)
+    ghost_floors(sc, rects, held, halo, halo * sc.cell, loose=tuple(ownerless) + GHOST_LOOSE.get(name, ()))
+    return sc, rects, held
+
+
+def ghost_state(case, meshes=1, flags=0):
+    """-> (sc, meshes, single, rec, rects, held, handle_of): the twins of a case stepped, the floors of ghost_case_floors
+    asserted on the single engine's records before any tile is asked, the ghosts of every mesh unpacked"""
+    name, shape, halo, phases, placed = case
+    sc = scene(name)
+    tiles, single, kept = ghost_twins(sc, shape, halo, ghost_case_weights(sc, shape, halo, placed), phases, flags, meshes=meshes)
+    rec = single.read_agents()
+    _, rects, held = ghost_case_floors(case, rec)
+    table = {}
+    for hlp, ids in kept:
+        handles = {e._planner_handles[id(hlp)] for e in tiles[0].engines}
+        assert len(handles) == 1  # (every engine numbers the planners alike)
+        table.update((int(i), min(handles)) for i in ids.tolist())
+    for mesh in tiles:
+        assert mesh_rects(mesh).tolist() == rects.tolist()
+        assert mesh.read_agents().tobytes() == rec.tobytes()
+        unpack_ghosts(mesh)
+        # (before the exchange a tile still holds the agents that walked across a cut in the last step: only now does
+        # every tile hold the agents that stand in its cells)
+        assert [len(e) for e in mesh.engines] == [len(own) for own, _ in held]
+    return sc, tiles, single, rec, rects, held, table.__getitem__
+
+
+RECUT_FROM = ((24,), (24,))  # the cuts a mesh is made with before test_a_recut_of_tiles_that_hold_ghosts moves them
+
+
+def ghost_recut_floors(sc, rec, before, halo=1, shape=(2, 2)):
+    """By TileLayout and numpy alone: what a re-cut of the mesh with the rectangles `before` must give for the records
+    `rec`, and that it can be got wrong: the rings hold at least 20 ghosts each, every edge moves, and histograms that
+    counted the ghosts as well would put an edge elsewhere.  -> (rects after the re-cut, agents per tile after it)"""
+    held = held_by_tiles(sc, before, rec, halo)
+    cut = layout(sc, shape, halo, rec=rec)
+    after = rects_of(cut.x_edges, cut.y_edges)
+    n_after = np.bincount(owners(after, sc, rec), minlength=len(after))
+    twice = layout(sc, shape, halo, rec=np.concatenate([rec] + [g for _, g in held]))
+    print(f"{sc.name}: cuts {cuts_of(before)} -> {cuts_of(after)}, tiles hold {n_after.tolist()}; the rings hold "
+          f"{[len(g) for _, g in held]} ghosts; histograms with the ghosts would cut at {cuts_of(rects_of(twice.x_edges, twice.y_edges))}")
+    assert min(len(g) for _, g in held) >= 20
+    assert all(a != b for a, b in zip(sum(cuts_of(before), []), sum(cuts_of(after), [])))
+    assert (twice.x_edges, twice.y_edges) != (cut.x_edges, cut.y_edges)
+    return after, n_after

@@ -374,8 +374,10 @@ def test_wide_ids_by_external_id(monkeypatch):
 
 
 def test_a_tile_engine_holding_ghosts_answers_for_the_agents_it_owns():
-    """The engines of a 2 x 2 mesh after 40 steps hold ghost rings; asked directly, each lists its owned agents only, and
-    the rows of the four together are the whole answer."""
+    """The engines of a 2 x 2 mesh asked directly between two steps, 40 steps in: each lists the agents it holds, and the
+    rows of the four together are the whole answer.  (Despite the name no tile holds a ghost here: a step leaves a tile
+    exactly the agents it stepped.  Tiles that do hold ghosts, after an unpack driven by the host, are asked in
+    test_gpu_queries_ghost_tiles.py.)"""
     from test_gpu_encounters_mesh import _crowd
     pts, group, grid = _crowd()
     mesh = NativeTileMesh(LocationHash2D(**grid), (2, 2), 1)
