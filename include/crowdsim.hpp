@@ -632,6 +632,32 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
     return counts;
   }
+  // The agents inside each polygon zone (cs_zone_agents, include/crowdstep_state.h "Agents in polygon zones"): zones are
+  // runs of `vertices_xy` (x0, y0, x1, y1, ...), one row (zone, id) per zone and agent inside it by the even-odd f64 rule of
+  // the header, ascending by (zone, id); `filter`: a selection the agents must match too.  `limit`: at most that many
+  // rows (the first ones); a listing of more than CS_PAIRS_MAX rows throws, count_zone_agents has no limit.
+  std::vector<cs_zone_agent> zone_agents(const std::vector<cs_zone>& zones, const std::vector<double>& vertices_xy,
+                                         const cs_selection* filter = nullptr, std::size_t limit = SIZE_MAX) {
+    std::vector<cs_zone_agent> out;
+    const std::size_t count = cs_zone_agents(engine_, zones.data(), zones.size(), vertices_xy.data(), vertices_xy.size() / 2, filter, nullptr, nullptr, 0);
+    if (count == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    std::size_t cap = std::min(count, limit);
+    if (!cap) return out;
+    if (count > CS_PAIRS_MAX) cap = 1;  // (refused by the library, with its message: no room is made for it here)
+    out.resize(cap);
+    const std::size_t n = cs_zone_agents(engine_, zones.data(), zones.size(), vertices_xy.data(), vertices_xy.size() / 2, filter, nullptr, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  // the number of rows of zone_agents(...) per zone, from one pass that lists nothing, exact whatever its size
+  std::vector<uint64_t> count_zone_agents(const std::vector<cs_zone>& zones, const std::vector<double>& vertices_xy,
+                                          const cs_selection* filter = nullptr) {
+    std::vector<uint64_t> counts(zones.size());
+    const std::size_t n = cs_zone_agents(engine_, zones.data(), zones.size(), vertices_xy.data(), vertices_xy.size() / 2, filter, counts.data(), nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return counts;
+  }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
     std::vector<AgentId> ids(cs_agent_count(engine_));
@@ -1055,6 +1081,32 @@ class TiledSimulation {
                                             const cs_selection* targets = nullptr) {
     std::vector<uint64_t> counts(legs.size());
     const std::size_t n = cs_mesh_leg_intervals(mesh_, legs.data(), legs.size(), distance, speed_max, targets, counts.data(), nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return counts;
+  }
+  // The agents inside each polygon zone (cs_mesh_zone_agents, include/crowdstep_state.h "Agents in polygon zones"): zones are
+  // runs of `vertices_xy` (x0, y0, x1, y1, ...), one row (zone, id) per zone and agent inside it by the even-odd f64 rule of
+  // the header, ascending by (zone, id); `filter`: a selection the agents must match too.  `limit`: at most that many
+  // rows (the first ones); a listing of more than CS_PAIRS_MAX rows throws, count_zone_agents has no limit.
+  std::vector<cs_zone_agent> zone_agents(const std::vector<cs_zone>& zones, const std::vector<double>& vertices_xy,
+                                         const cs_selection* filter = nullptr, std::size_t limit = SIZE_MAX) {
+    std::vector<cs_zone_agent> out;
+    const std::size_t count = cs_mesh_zone_agents(mesh_, zones.data(), zones.size(), vertices_xy.data(), vertices_xy.size() / 2, filter, nullptr, nullptr, 0);
+    if (count == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    std::size_t cap = std::min(count, limit);
+    if (!cap) return out;
+    if (count > CS_PAIRS_MAX) cap = 1;  // (refused by the library, with its message: no room is made for it here)
+    out.resize(cap);
+    const std::size_t n = cs_mesh_zone_agents(mesh_, zones.data(), zones.size(), vertices_xy.data(), vertices_xy.size() / 2, filter, nullptr, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  // the number of rows of zone_agents(...) per zone, from one pass that lists nothing, exact whatever its size
+  std::vector<uint64_t> count_zone_agents(const std::vector<cs_zone>& zones, const std::vector<double>& vertices_xy,
+                                          const cs_selection* filter = nullptr) {
+    std::vector<uint64_t> counts(zones.size());
+    const std::size_t n = cs_mesh_zone_agents(mesh_, zones.data(), zones.size(), vertices_xy.data(), vertices_xy.size() / 2, filter, counts.data(), nullptr, 0);
     if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
     return counts;
   }

@@ -634,6 +634,71 @@ size_t cs_leg_intervals(cs_engine*, const cs_leg* legs, size_t n, double distanc
 size_t cs_mesh_leg_intervals(cs_mesh*, const cs_leg* legs, size_t n, double distance, double speed_max,
                              const cs_selection* targets, uint64_t* out_counts, cs_leg_interval* out, size_t cap);
 
+/* Agents in polygon zones.  The regions a selection can name are an axis-aligned rectangle and a circle; the zones of a
+ * building (rooms and corridors drawn in a traffic editor, a lift cabin that stands at an angle, an L-shaped lobby, the
+ * keep-out region in front of a door, the catchment of a sink) are polygons.  cs_zone_agents counts, and lists, the agents
+ * inside each of up to CS_ZONES_MAX polygons in one call.  A zone is a run of `count` vertices of the call's vertex
+ * array (a vertex is two doubles, x then y); the ring closes from its last vertex to its first.  Zones may overlap, and
+ * they may share vertices: their runs may overlap.
+ *
+ * WHO TAKES PART.  An agent is the record cs_read_agents returns for it at that moment, (x, y) its reported f64 position.
+ * It takes part by the rule of cs_close_pairs: a finite position inside the grid's own rectangle (the global grid's on a
+ * tile engine and on a mesh); on a tile whose arrays hold ghosts only owned agents; `filter` is judged as for
+ * cs_select_agents, NULL is everyone.  Agents the index never took take no part, nor do clamped, aliased or NaN agents.
+ *
+ * THE RULE.  The box of a zone is the exact minimum and maximum of its vertices' coordinates, bx0, bx1, by0, by1.  Every
+ * operation of the ring test is one f64 operation rounded once: no contraction, no reciprocal, no f32 pre-reject.  For
+ * every edge of the ring, vertex i to vertex (i + 1) % count, let (lx, ly) be the end with the smaller y and (hx, hy) the
+ * other (so two zones that share an edge, given by the same two vertices, evaluate it to the same bits whichever way each
+ * runs along it).  An edge with ly == hy never straddles; otherwise
+ *     the edge STRADDLES iff ly <= y && y < hy
+ *     a straddling edge CROSSES iff c > 0,  ex = hx - lx;  ey = hy - ly;  px = x - lx;  py = y - ly;  c = ex*py - ey*px
+ *     the agent is IN THE ZONE iff bx0 <= x && x <= bx1 && by0 <= y && y <= by1 and the number of crossing edges is odd
+ * This is the even-odd rule, so concave and self-intersecting rings are defined.  The box is part of the rule.  It is what
+ * lets the library visit only the cells the box touches and still be exact: for x > bx1, or y outside [by0, by1], no edge
+ * crosses anyway (no edge straddles a y outside the box; for x beyond both ends of a straddling edge px >= |ex| and
+ * py <= ey as rounded, products round monotonically, so c <= 0), but for x < bx0 the rounding of c could say otherwise,
+ * and the box settles it.  What follows: the ring (x0,y0) (x1,y0) (x1,y1) (x0,y1) holds, in either winding, exactly the
+ * participants CS_SEL_RECT selects with the same numbers, x0 <= x < x1 && y0 <= y < y1; of zones that tile a region with
+ * matching vertices every agent in the region is in an odd number, because shared edges are judged alike, and in exactly
+ * one where all the arithmetic is exact (small dyadic coordinates).
+ *
+ * THE ANSWER.  Every row (zone, id) once, ascending by (zone, id).  The call returns the full count and writes the first
+ * min(count, cap) rows, nothing beyond them; out_counts[k], if given, is the full number of rows of zone k whatever cap
+ * is.  out == NULL or cap == 0 asks for the counts only: one pass that makes no row, with a 64-bit total on the device,
+ * and no limit.  With cap > 0 a count above CS_PAIRS_MAX is refused (SIZE_MAX, "too many zone agents to list", the engine
+ * usable).  n == 0 returns 0.
+ *
+ * REFUSALS (SIZE_MAX; nothing is written, out_counts included; the engine or mesh stays usable; the text names the first
+ * bad zone): null zones or vertices with n > 0, n > CS_ZONES_MAX, n_vertices > CS_ZONE_VERTICES_MAX, a filter that
+ * cs_select_agents refuses, a zone with count < 3, with first + count > n_vertices, with flags != 0, or with a NaN or
+ * infinite vertex.
+ *
+ * Queued steps complete first and an Err of one of them is the call's; no events, the last step report is left alone,
+ * nothing is renumbered (the arrays may be sorted by cell, as by the other spatial queries), and a twin that never asks
+ * stays byte-equal. */
+#define CS_ZONES_MAX         65536u     /* zones in one call                    */
+#define CS_ZONE_VERTICES_MAX (1u << 20) /* vertices of all zones of one call    */
+typedef struct cs_zone {       /* 16 bytes: one polygon, a run of the call's vertex array          */
+  uint64_t first;              /* index of its first vertex (a vertex is two doubles, x then y)    */
+  uint32_t count;              /* its vertices, >= 3; the ring closes from the last to the first   */
+  uint32_t flags;              /* 0                                                                */
+} cs_zone;
+typedef struct cs_zone_agent { /* 16 bytes: agent `id` is in zone `zone`                           */
+  uint64_t zone;               /* index of the zone in the call                                    */
+  uint64_t id;                 /* the agent (the external id under CS_CFG_WIDE_IDS)                */
+} cs_zone_agent;
+size_t cs_zone_agents(cs_engine*, const cs_zone* zones, size_t n, const double* vertices_xy, size_t n_vertices,
+                      const cs_selection* filter, uint64_t* out_counts /* n entries; may be NULL */,
+                      cs_zone_agent* out, size_t cap);
+/* The same on a mesh.  Collective: every rank passes the same zones and gets the single engine's answer, byte for byte.
+ * Every tile runs ALL zones against the agents it owns; one gather carries the per-zone counts (agents are disjoint
+ * across tiles, so counts add, and every rank decides the CS_PAIRS_MAX refusal from them alike); when listing, one more
+ * carries each rank's first rows, and every rank merges the (zone, id)-sorted runs.  No halo exchange is made and the
+ * step's exchange state is not touched.  A tile that fails makes every rank return SIZE_MAX. */
+size_t cs_mesh_zone_agents(cs_mesh*, const cs_zone* zones, size_t n, const double* vertices_xy, size_t n_vertices,
+                           const cs_selection* filter, uint64_t* out_counts, cs_zone_agent* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -261,6 +261,8 @@ CS_NO_NEIGHBOUR = 0xFFFFFFFFFFFFFFFF
 CS_NO_HIT = 0xFFFFFFFFFFFFFFFF
 CS_RAYS_MAX = 1 << 20
 CS_LEGS_MAX = 1 << 20
+CS_ZONES_MAX = 65536
+CS_ZONE_VERTICES_MAX = 1 << 20
 
 
 class Selection(C.Structure):
@@ -331,6 +333,21 @@ class LegInterval(C.Structure):
 LEG_INTERVAL_DTYPE = [("leg", "<u8"), ("id", "<u8"), ("s_in", "<f8"), ("s_out", "<f8")]
 
 
+class Zone(C.Structure):
+    """cs_zone: one polygon of cs_zone_agents, a run of `count` vertices of the call's vertex array from `first` on
+    (include/crowdstep_state.h)"""
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ZoneAgent(C.Structure):
+    """cs_zone_agent: one row of cs_zone_agents: agent `id` is in zone `zone` (include/crowdstep_state.h)"""
+    _fields_ = [("zone", C.c_uint64), ("id", C.c_uint64)]
+
+
+ZONE_DTYPE = [("first", "<u8"), ("count", "<u4"), ("flags", "<u4")]
+ZONE_AGENT_DTYPE = [("zone", "<u8"), ("id", "<u8")]
+
+
 _PAIRS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.POINTER(IdPair), C.POINTER(C.c_double),
                C.c_size_t]
 _CLUSTERS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -343,6 +360,8 @@ _RAYS_ARGS = [C.c_void_p, C.POINTER(Ray), C.c_size_t, C.c_double, C.POINTER(Sele
 _LEGS_ARGS = [C.c_void_p, C.POINTER(Leg), C.c_size_t, C.c_double, C.c_double, C.POINTER(Selection), C.POINTER(LegHit)]
 _LEG_INTERVALS_ARGS = [C.c_void_p, C.POINTER(Leg), C.c_size_t, C.c_double, C.c_double, C.POINTER(Selection),
                        C.POINTER(C.c_uint64), C.POINTER(LegInterval), C.c_size_t]
+_ZONE_AGENTS_ARGS = [C.c_void_p, C.POINTER(Zone), C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.POINTER(Selection),
+                     C.POINTER(C.c_uint64), C.POINTER(ZoneAgent), C.c_size_t]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -383,6 +402,8 @@ STATE_SYMBOLS = {
     "cs_mesh_leg_conflicts": (C.c_size_t, list(_LEGS_ARGS)),
     "cs_leg_intervals": (C.c_size_t, list(_LEG_INTERVALS_ARGS)),
     "cs_mesh_leg_intervals": (C.c_size_t, list(_LEG_INTERVALS_ARGS)),
+    "cs_zone_agents": (C.c_size_t, list(_ZONE_AGENTS_ARGS)),
+    "cs_mesh_zone_agents": (C.c_size_t, list(_ZONE_AGENTS_ARGS)),
 }
 
 

@@ -970,6 +970,62 @@ def free_intervals_of(leg_intervals, points, t0, t1, distance, speed_max, ignore
     return free_spans(offsets, spans, legs["t0"], legs["t1"])
 
 
+ZONE_DTYPE = np.dtype(_abi.ZONE_DTYPE)
+ZONE_AGENT_DTYPE = np.dtype(_abi.ZONE_AGENT_DTYPE)
+assert ZONE_DTYPE.itemsize == C.sizeof(_abi.Zone) == 16 and ZONE_AGENT_DTYPE.itemsize == C.sizeof(_abi.ZoneAgent) == 16
+
+
+def zones_array(polygons):
+    """The polygons of zone_agents as the library takes them: polygons, a list of (k, 2) arrays of (x, y) vertices (k >= 3,
+    the ring closes from the last to the first) -> (zones, a ZONE_DTYPE array of one run per polygon; vertices, float64
+    (n_vertices, 2), the polygons' vertices one after the other).  A pair (zones, vertices) that is already of this form
+    (zones that share vertices are written that way) is passed through."""
+    if isinstance(polygons, tuple) and len(polygons) == 2 and getattr(polygons[0], "dtype", None) == ZONE_DTYPE:
+        return (np.ascontiguousarray(polygons[0], dtype=ZONE_DTYPE),
+                np.ascontiguousarray(polygons[1], dtype=np.float64).reshape(-1, 2))
+    rings = [np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in polygons]
+    zones = np.zeros(len(rings), dtype=ZONE_DTYPE)
+    zones["count"] = [len(r) for r in rings]
+    zones["first"] = np.concatenate([[0], np.cumsum(zones["count"].astype(np.uint64))[:-1]]) if len(rings) else []
+    vertices = np.concatenate(rings) if rings else np.zeros((0, 2), dtype=np.float64)
+    return zones, np.ascontiguousarray(vertices, dtype=np.float64)
+
+
+def zone_agents_call(fn, handle, zones, vertices, sel, want_counts, cap):
+    """cs_zone_agents / cs_mesh_zone_agents with room for `cap` rows -> (the full count, or None on error; the per-zone
+    uint64 counts, or None; the first min(count, cap) rows as a ZONE_AGENT_DTYPE array).  cap == 0: counts only."""
+    zones = np.ascontiguousarray(zones, dtype=ZONE_DTYPE)
+    vertices = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 2)
+    n, cap = len(zones), max(int(cap), 0)
+    counts = np.zeros(max(n, 1), dtype=np.uint64) if want_counts else None
+    rows = np.zeros(max(cap, 1), dtype=ZONE_AGENT_DTYPE)
+    got = fn(handle, zones.ctypes.data_as(C.POINTER(_abi.Zone)) if n else None, n,
+             vertices.ctypes.data_as(C.POINTER(C.c_double)) if len(vertices) else None, len(vertices),
+             C.byref(sel) if sel is not None else None,
+             counts.ctypes.data_as(C.POINTER(C.c_uint64)) if want_counts else None,
+             rows.ctypes.data_as(C.POINTER(_abi.ZoneAgent)) if cap else None, cap)
+    if got == _SIZE_MAX:
+        return None, None, rows[:0].copy()
+    return got, (counts[:n].copy() if want_counts else None), rows[:min(got, cap)].copy()
+
+
+def zone_agents_of(fn, handle, handle_of, err, polygons, filter, limit):
+    """zone_agents and count_zone_agents of Simulation and NativeTileMesh.  limit=None lists every row (one counting call
+    first), limit=0 only counts -> (count, per-zone counts, rows)"""
+    zones, vertices = zones_array(polygons)
+    sel = None if filter is None else selection_struct(filter, handle_of)
+    if limit is None:
+        limit, _, _ = zone_agents_call(fn, handle, zones, vertices, sel, False, 0)
+        if limit is None:
+            raise err()
+        if limit > _abi.CS_PAIRS_MAX:
+            limit = 1  # (the listing is refused by the library, with its message: no room is made for it here)
+    n, counts, rows = zone_agents_call(fn, handle, zones, vertices, sel, True, limit)
+    if n is None:
+        raise err()
+    return int(n), counts, rows
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -1456,6 +1512,27 @@ class Simulation:
         value per point, seconds from now) in one leg_intervals call.  Returns, per point, the list of (start, end)
         absolute times inside [t0, t1] during which nobody slower than speed_max is within `distance` of it, ascending."""
         return free_intervals_of(self.leg_intervals, points, t0, t1, distance, speed_max, ignore, targets)
+
+    zones_array = staticmethod(zones_array)
+
+    def zone_agents(self, polygons, *, filter=None, limit=None):
+        """The agents inside each polygon zone, on the device (cs_zone_agents).  polygons: a list of (k, 2) arrays of
+        (x, y) vertices, or the (zones, vertices) of zones_array; zones may overlap.  Returns (rows, counts): rows a
+        structured array (zone, id) ascending by (zone, id), counts the full number of rows of each zone (uint64).  An
+        agent is in a zone by the even-odd rule of include/crowdstep_state.h ("Agents in polygon zones"), in f64, bit for
+        bit: a ring (x0,y0) (x1,y0) (x1,y1) (x0,y1) holds exactly the agents rect=(x0, y0, x1, y1) selects.  filter: a
+        selection (as for select_agents) the agents must match too.  limit: at most that many rows (the first ones); None
+        lists all, and above _abi.CS_PAIRS_MAX raises, count_zone_agents has no limit.  Changes nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_zone_agents", "zone_agents")
+        _, counts, rows = zone_agents_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, polygons,
+                                         filter, limit)
+        return rows, counts
+
+    def count_zone_agents(self, polygons, filter=None):
+        """The number of agents in each zone of zone_agents(...) (uint64, one entry per zone), from one pass that lists
+        nothing, exact whatever its size."""
+        fn = state_fn(self._lib, self.backend, "cs_zone_agents", "zone_agents")
+        return zone_agents_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, polygons, filter, 0)[1]
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

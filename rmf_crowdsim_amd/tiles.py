@@ -865,6 +865,27 @@ class NativeTileMesh:
         from .simulation import free_intervals_of
         return free_intervals_of(self.leg_intervals, points, t0, t1, distance, speed_max, ignore, targets)
 
+    @staticmethod
+    def zones_array(polygons):
+        """Simulation.zones_array"""
+        from .simulation import zones_array
+        return zones_array(polygons)
+
+    def zone_agents(self, polygons, *, filter=None, limit=None):
+        """Simulation.zone_agents on the mesh (cs_mesh_zone_agents): the single engine's answer, byte for byte (collective
+        in the distributed form).  Every tile runs all zones against the agents it owns; one gather carries the per-zone
+        counts, one more the rows, which every rank merges by (zone, id)."""
+        from .simulation import state_fn, zone_agents_of
+        fn = state_fn(self._lib, "mesh", "cs_mesh_zone_agents", "zone_agents")
+        _, counts, rows = zone_agents_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, polygons, filter, limit)
+        return rows, counts
+
+    def count_zone_agents(self, polygons, filter=None):
+        """Simulation.count_zone_agents on the mesh (collective in the distributed form): only counts travel."""
+        from .simulation import state_fn, zone_agents_of
+        fn = state_fn(self._lib, "mesh", "cs_mesh_zone_agents", "zone_agents")
+        return zone_agents_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, polygons, filter, 0)[1]
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
