@@ -658,6 +658,34 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
     return counts;
   }
+  // Who walks through each gate within its window (cs_gate_crossings, include/crowdstep_state.h "Who crosses a line"): a
+  // gate is the segment A -> B watched from t0 to t1; one row (gate, dir, id, s, u) per gate and agent that crosses it if
+  // it keeps its velocity, ascending by (gate, id): at t0 + s, at A + u * (B - A), ending on the left (dir +1) or the
+  // right (dir -1) of A -> B, bit for bit.  Agents at or above speed_max are not considered; `filter`: a selection the
+  // agents must match too.  `limit`: at most that many rows (the first ones); a listing of more than CS_PAIRS_MAX rows
+  // throws, count_gate_crossings has no limit.
+  std::vector<cs_gate_crossing> gate_crossings(const std::vector<cs_gate>& gates, double speed_max,
+                                               const cs_selection* filter = nullptr, std::size_t limit = SIZE_MAX) {
+    std::vector<cs_gate_crossing> out;
+    const std::size_t count = cs_gate_crossings(engine_, gates.data(), gates.size(), speed_max, filter, nullptr, nullptr, 0);
+    if (count == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    std::size_t cap = std::min(count, limit);
+    if (!cap) return out;
+    if (count > CS_PAIRS_MAX) cap = 1;  // (refused by the library, with its message: no room is made for it here)
+    out.resize(cap);
+    const std::size_t n = cs_gate_crossings(engine_, gates.data(), gates.size(), speed_max, filter, nullptr, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  // the rows of gate_crossings(...) per gate and direction: [2k] dir +1, [2k + 1] dir -1; one pass that lists nothing
+  std::vector<uint64_t> count_gate_crossings(const std::vector<cs_gate>& gates, double speed_max,
+                                             const cs_selection* filter = nullptr) {
+    std::vector<uint64_t> counts(2 * gates.size());
+    const std::size_t n = cs_gate_crossings(engine_, gates.data(), gates.size(), speed_max, filter, counts.data(), nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_last_error(engine_));
+    return counts;
+  }
   // remove_agents(select_agents(sel)): the same events and planner callbacks, in ascending id; returns the removed ids
   std::vector<AgentId> remove_selected(const cs_selection& sel) {
     std::vector<AgentId> ids(cs_agent_count(engine_));
@@ -1107,6 +1135,32 @@ class TiledSimulation {
                                           const cs_selection* filter = nullptr) {
     std::vector<uint64_t> counts(zones.size());
     const std::size_t n = cs_mesh_zone_agents(mesh_, zones.data(), zones.size(), vertices_xy.data(), vertices_xy.size() / 2, filter, counts.data(), nullptr, 0);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return counts;
+  }
+  // Who walks through each gate within its window (cs_mesh_gate_crossings, include/crowdstep_state.h "Who crosses a
+  // line"): one row (gate, dir, id, s, u) per gate and agent that crosses it, ascending by (gate, id), bit for bit the
+  // single engine's.  `limit`: at most that many rows (the first ones); a listing of more than CS_PAIRS_MAX rows throws,
+  // count_gate_crossings has no limit.
+  std::vector<cs_gate_crossing> gate_crossings(const std::vector<cs_gate>& gates, double speed_max,
+                                               const cs_selection* filter = nullptr, std::size_t limit = SIZE_MAX) {
+    std::vector<cs_gate_crossing> out;
+    const std::size_t count = cs_mesh_gate_crossings(mesh_, gates.data(), gates.size(), speed_max, filter, nullptr, nullptr, 0);
+    if (count == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    std::size_t cap = std::min(count, limit);
+    if (!cap) return out;
+    if (count > CS_PAIRS_MAX) cap = 1;  // (refused by the library, with its message: no room is made for it here)
+    out.resize(cap);
+    const std::size_t n = cs_mesh_gate_crossings(mesh_, gates.data(), gates.size(), speed_max, filter, nullptr, out.data(), cap);
+    if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
+    out.resize(std::min(n, cap));
+    return out;
+  }
+  // the rows of gate_crossings(...) per gate and direction: [2k] dir +1, [2k + 1] dir -1; one pass that lists nothing
+  std::vector<uint64_t> count_gate_crossings(const std::vector<cs_gate>& gates, double speed_max,
+                                             const cs_selection* filter = nullptr) {
+    std::vector<uint64_t> counts(2 * gates.size());
+    const std::size_t n = cs_mesh_gate_crossings(mesh_, gates.data(), gates.size(), speed_max, filter, counts.data(), nullptr, 0);
     if (n == SIZE_MAX) throw std::runtime_error(cs_mesh_last_error(mesh_));
     return counts;
   }

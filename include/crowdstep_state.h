@@ -699,6 +699,82 @@ size_t cs_zone_agents(cs_engine*, const cs_zone* zones, size_t n, const double* 
 size_t cs_mesh_zone_agents(cs_mesh*, const cs_zone* zones, size_t n, const double* vertices_xy, size_t n_vertices,
                            const cs_selection* filter, uint64_t* out_counts, cs_zone_agent* out, size_t cap);
 
+/* Who crosses a line.  A door threshold, a turnstile, a crosswalk, a platform edge and a light barrier are all a segment,
+ * and the question is who walks through it and in which direction: an automatic door asks whether anyone will pass its
+ * threshold within the next 1.5 s and from which side, a traffic planner how many people are about to cross a lane, a
+ * flow meter for the flow through a bottleneck per direction.  A GATE is the segment from A = (ax, ay) to B = (bx, by)
+ * with a time window t0 <= t1, in seconds from now; cs_gate_crossings counts, and lists, for up to CS_GATES_MAX gates
+ * in one call the agents that cross each within its window if everybody keeps walking as they do now.
+ *
+ * An agent is the record cs_read_agents returns for it: x, y in f64 and vx, vy the f32 velocity widened to f64, kept
+ * constant.  Agents are points, as for zones.  PARTICIPANTS are the pairs' participants: the agents whose reported
+ * position is finite and inside the grid's own rectangle (on a tile or a mesh: the global one; on a tile engine with
+ * ghosts only owned agents).  `filter` is judged as for cs_select_agents; NULL is everyone.
+ *
+ * THE RULE, for gate (ax, ay, bx, by, t0, t1) and participant q, with S2 = speed_max * speed_max and T = t1 - t0, every
+ * operation one f64 operation rounded once (no contraction, no reciprocal, no f32 pre-reject, the correctly rounded
+ * division):
+ *     ss = vx*vx + vy*vy;            SLOW ENOUGH iff ss < S2   (else q is not considered; a NaN is not)
+ *     px = x + vx*t0;  py = y + vy*t0                          (where q is when the window opens)
+ *     ex = bx - ax;    ey = by - ay
+ *     rx = px - ax;    ry = py - ay
+ *     c0 = ex*ry - ey*rx             (the side at t0: > 0 is left of A->B)
+ *     cv = ex*vy - ey*vx             (the rate of change of the side)
+ *     cu = rx*vy - ry*vx
+ *     miss unless (cv > 0 && c0 <= 0) || (cv < 0 && c0 >= 0)   (parallel, A == B, moving away, a NaN: miss)
+ *     s  = (-c0) / cv;  if !(s > 0): s = +0.0                  (on the line at t0 and moving off it: s = +0.0)
+ *     u  = cu / cv
+ *     CROSSING iff s < T && u >= 0 && u < 1
+ *     dir = +1 if cv > 0 (the agent ends on the left of A->B), -1 otherwise
+ * The crossing happens at time t0 + s at the point A + u * (B - A).  The interval of u is half-open, so gates that chain
+ * through shared vertices (a polyline) count a walker once wherever every operation is exact (small dyadic
+ * coordinates).  A straight walker crosses a line at most once, so (gate, id) is a unique key.  T == 0 gives nothing; a
+ * gate with A == B is accepted and crosses nobody; speed_max = +inf and any finite t1 are allowed, the grid being finite.
+ *
+ * speed_max is part of the definition for the reason it is for legs: a slow-enough agent that crosses within the window
+ * stands NOW within speed_max * t1 of the segment, and the device looks no further than that reach plus one spare cell.
+ * The rule's roundings place the crossing off by about 2^-51 |r| / sin(angle between the gate and the velocity), far
+ * below that cell; only a walker that is parallel to an oblique gate and collinear with it to within the rounding of cv
+ * and c0 themselves (no such case exists where the products are exact: axis-aligned gates, dyadic coordinates) can be a
+ * crossing by rounding alone, and it is listed when it stands within the reach and not when it stands beyond it.  A host
+ * that wants nobody left out passes a bound at or above its planners' top speed.
+ *
+ * THE ANSWER.  Every row once, ascending by (gate, id); ids are external ids under CS_CFG_WIDE_IDS.  The call returns the
+ * full count and writes the first min(count, cap) rows, nothing beyond them; out_counts[2k] and out_counts[2k + 1], if
+ * given, are the full numbers of rows of gate k with dir +1 and with dir -1, whatever cap is.  out == NULL or cap == 0
+ * asks for the counts only: one pass that makes no row, with a 64-bit total on the device, and no limit.  With cap > 0 a
+ * count above CS_PAIRS_MAX is refused (SIZE_MAX, "too many crossings to list", the engine usable).  n == 0 returns 0.
+ *
+ * REFUSALS (SIZE_MAX; nothing is written, out_counts included; the engine or mesh stays usable; the text names the first
+ * bad gate): n > CS_GATES_MAX, gates == NULL with n > 0, a NaN or negative speed_max, a gate with a non-finite field,
+ * with t0 < 0 or with t1 < t0, a selection cs_select_agents refuses.
+ *
+ * Queued steps complete first and an Err of one of them is the call's; no events, the last step report is left alone,
+ * nothing is renumbered, and a twin that never asks stays byte-equal. */
+#define CS_GATES_MAX (1u << 20)         /* gates of one call */
+typedef struct cs_gate {                /* 48 bytes */
+  double ax, ay;        /* the end A, world coordinates, finite                                */
+  double bx, by;        /* the end B; left and right are those of somebody looking from A to B */
+  double t0, t1;        /* 0 <= t0 <= t1, both finite, seconds from now                        */
+} cs_gate;
+typedef struct cs_gate_crossing {       /* 32 bytes */
+  uint32_t gate;        /* index of the gate in the call                                       */
+  int32_t  dir;         /* +1: the agent ends on the left of A->B, -1: on the right            */
+  uint64_t id;          /* the agent (the external id under CS_CFG_WIDE_IDS)                   */
+  double   s;           /* seconds after t0 at which it crosses, bit for bit; never -0.0       */
+  double   u;           /* where: the point A + u * (B - A), 0 <= u < 1, bit for bit           */
+} cs_gate_crossing;
+size_t cs_gate_crossings(cs_engine*, const cs_gate* gates, size_t n, double speed_max, const cs_selection* filter,
+                         uint64_t* out_counts /* 2n entries: [2k] dir +1, [2k+1] dir -1; may be NULL */,
+                         cs_gate_crossing* out, size_t cap);
+/* The same on a mesh.  Collective: every rank passes the same gates and gets the single engine's answer, byte for byte.
+ * Every tile runs ALL gates against the agents it owns; one gather carries the 2n counts (agents are disjoint across
+ * tiles, so counts add, and every rank decides the CS_PAIRS_MAX refusal from them alike); when listing, one more carries
+ * each rank's first rows, and every rank merges the (gate, id)-sorted runs.  No halo exchange is made and the step's
+ * exchange state is not touched.  A tile that fails makes every rank return SIZE_MAX. */
+size_t cs_mesh_gate_crossings(cs_mesh*, const cs_gate* gates, size_t n, double speed_max, const cs_selection* filter,
+                              uint64_t* out_counts, cs_gate_crossing* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -348,6 +348,23 @@ ZONE_DTYPE = [("first", "<u8"), ("count", "<u4"), ("flags", "<u4")]
 ZONE_AGENT_DTYPE = [("zone", "<u8"), ("id", "<u8")]
 
 
+class Gate(C.Structure):
+    """cs_gate: one gate of cs_gate_crossings, the segment A -> B watched from t0 to t1 (include/crowdstep_state.h)"""
+    _fields_ = [("ax", C.c_double), ("ay", C.c_double), ("bx", C.c_double), ("by", C.c_double), ("t0", C.c_double),
+                ("t1", C.c_double)]
+
+
+class GateCrossing(C.Structure):
+    """cs_gate_crossing: one row of cs_gate_crossings: agent `id` crosses gate `gate` at t0 + s, at A + u * (B - A), and
+    ends on the left (dir +1) or the right (dir -1) of A -> B (include/crowdstep_state.h)"""
+    _fields_ = [("gate", C.c_uint32), ("dir", C.c_int32), ("id", C.c_uint64), ("s", C.c_double), ("u", C.c_double)]
+
+
+GATE_DTYPE = [("ax", "<f8"), ("ay", "<f8"), ("bx", "<f8"), ("by", "<f8"), ("t0", "<f8"), ("t1", "<f8")]
+GATE_CROSSING_DTYPE = [("gate", "<u4"), ("dir", "<i4"), ("id", "<u8"), ("s", "<f8"), ("u", "<f8")]
+CS_GATES_MAX = 1 << 20
+
+
 _PAIRS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.POINTER(Selection), C.POINTER(IdPair), C.POINTER(C.c_double),
                C.c_size_t]
 _CLUSTERS_ARGS = [C.c_void_p, C.c_double, C.POINTER(Selection), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -362,6 +379,8 @@ _LEG_INTERVALS_ARGS = [C.c_void_p, C.POINTER(Leg), C.c_size_t, C.c_double, C.c_d
                        C.POINTER(C.c_uint64), C.POINTER(LegInterval), C.c_size_t]
 _ZONE_AGENTS_ARGS = [C.c_void_p, C.POINTER(Zone), C.c_size_t, C.POINTER(C.c_double), C.c_size_t, C.POINTER(Selection),
                      C.POINTER(C.c_uint64), C.POINTER(ZoneAgent), C.c_size_t]
+_GATE_CROSSINGS_ARGS = [C.c_void_p, C.POINTER(Gate), C.c_size_t, C.c_double, C.POINTER(Selection), C.POINTER(C.c_uint64),
+                        C.POINTER(GateCrossing), C.c_size_t]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -404,6 +423,8 @@ STATE_SYMBOLS = {
     "cs_mesh_leg_intervals": (C.c_size_t, list(_LEG_INTERVALS_ARGS)),
     "cs_zone_agents": (C.c_size_t, list(_ZONE_AGENTS_ARGS)),
     "cs_mesh_zone_agents": (C.c_size_t, list(_ZONE_AGENTS_ARGS)),
+    "cs_gate_crossings": (C.c_size_t, list(_GATE_CROSSINGS_ARGS)),
+    "cs_mesh_gate_crossings": (C.c_size_t, list(_GATE_CROSSINGS_ARGS)),
 }
 
 

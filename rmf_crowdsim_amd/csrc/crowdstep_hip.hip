@@ -31,6 +31,7 @@
 //   cs_legs.hip.inc           timed path legs against the moving crowd: who comes within a distance first (the same header)
 //   cs_leg_intervals.hip.inc  the same legs, the complete list: every agent that enters a leg, when it enters and leaves
 //   cs_zones.hip.inc          polygon zones: the agents inside each, counted and listed (the same header)
+//   cs_gates.hip.inc          lines that are crossed: who walks through each gate, which way, when and where
 //   this file                 includes + the extern "C" boundary
 //
 // Device state is f32 and CELL-RELATIVE: an agent is (stored cell, offset from
@@ -1308,4 +1309,5 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_rays.hip.inc"
 #include "cs_legs.hip.inc"
 #include "cs_leg_intervals.hip.inc"
+#include "cs_gates.hip.inc"
 #include "cs_zones.hip.inc"

@@ -1026,6 +1026,69 @@ def zone_agents_of(fn, handle, handle_of, err, polygons, filter, limit):
     return int(n), counts, rows
 
 
+GATE_DTYPE = np.dtype(_abi.GATE_DTYPE)
+GATE_CROSSING_DTYPE = np.dtype(_abi.GATE_CROSSING_DTYPE)
+assert GATE_DTYPE.itemsize == C.sizeof(_abi.Gate) == 48
+assert GATE_CROSSING_DTYPE.itemsize == C.sizeof(_abi.GateCrossing) == 32
+
+
+def gates_array(segments, t0=0.0, t1=1.0):
+    """The GATE_DTYPE array of n gates: segments is (n, 4) rows (ax, ay, bx, by), or (n, 2, 2) pairs of points A, B; t0 and
+    t1 (seconds from now) one value for all or one per gate.  Left and right are those of somebody looking from A to B."""
+    seg = np.asarray(segments, dtype=np.float64).reshape(-1, 4)
+    n = np.broadcast_shapes((len(seg),), np.shape(t0), np.shape(t1))
+    if len(n) != 1:
+        raise ValueError("gate_crossings: t0 and t1 are scalars or one value per gate")
+    gates = np.zeros(n[0], dtype=GATE_DTYPE)
+    gates["ax"], gates["ay"], gates["bx"], gates["by"] = seg[:, 0], seg[:, 1], seg[:, 2], seg[:, 3]
+    gates["t0"] = np.asarray(t0, dtype=np.float64)
+    gates["t1"] = np.asarray(t1, dtype=np.float64)
+    return gates
+
+
+def path_gates(points, t0, t1):
+    """The chain of gates along a polyline of k + 1 points: gate i runs from point i to point i + 1, all with the window
+    t0 .. t1.  The gates share their vertices and u is half-open, so a walker that passes through a vertex belongs to one
+    gate of the chain wherever the arithmetic is exact."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    if len(p) < 2:
+        raise ValueError("path_gates: at least two points")
+    return gates_array(np.concatenate([p[:-1], p[1:]], axis=1), t0, t1)
+
+
+def gate_crossings_call(fn, handle, gates, speed_max, sel, want_counts, cap):
+    """cs_gate_crossings / cs_mesh_gate_crossings with room for `cap` rows -> (the full count, or None on error; the
+    uint64 counts (n, 2), column 0 dir +1 and column 1 dir -1, or None; the first min(count, cap) rows as a
+    GATE_CROSSING_DTYPE array).  cap == 0: counts only."""
+    gates = np.ascontiguousarray(gates, dtype=GATE_DTYPE)
+    n, cap = len(gates), max(int(cap), 0)
+    counts = np.zeros((max(n, 1), 2), dtype=np.uint64) if want_counts else None
+    rows = np.zeros(max(cap, 1), dtype=GATE_CROSSING_DTYPE)
+    got = fn(handle, gates.ctypes.data_as(C.POINTER(_abi.Gate)) if n else None, n, float(speed_max),
+             C.byref(sel) if sel is not None else None,
+             counts.ctypes.data_as(C.POINTER(C.c_uint64)) if want_counts else None,
+             rows.ctypes.data_as(C.POINTER(_abi.GateCrossing)) if cap else None, cap)
+    if got == _SIZE_MAX:
+        return None, None, rows[:0].copy()
+    return got, (counts[:n].copy() if want_counts else None), rows[:min(got, cap)].copy()
+
+
+def gate_crossings_of(fn, handle, handle_of, err, gates, speed_max, filter, limit):
+    """gate_crossings and count_gate_crossings of Simulation and NativeTileMesh.  limit=None lists every row (one counting
+    call first), limit=0 only counts -> (count, counts (n, 2), rows)"""
+    sel = None if filter is None else selection_struct(filter, handle_of)
+    if limit is None:
+        limit, _, _ = gate_crossings_call(fn, handle, gates, speed_max, sel, False, 0)
+        if limit is None:
+            raise err()
+        if limit > _abi.CS_PAIRS_MAX:
+            limit = 1  # (the listing is refused by the library, with its message: no room is made for it here)
+    n, counts, rows = gate_crossings_call(fn, handle, gates, speed_max, sel, True, limit)
+    if n is None:
+        raise err()
+    return int(n), counts, rows
+
+
 def _agents_dict(arr):
     return {int(r["id"]): Agent(int(r["id"]), np.array([r["x"], r["y"]]), np.array([r["vx"], r["vy"]]),
                                 int(r["next_waypoint"]), float(r["eyesight_range"]))
@@ -1533,6 +1596,28 @@ class Simulation:
         nothing, exact whatever its size."""
         fn = state_fn(self._lib, self.backend, "cs_zone_agents", "zone_agents")
         return zone_agents_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, polygons, filter, 0)[1]
+
+    def gate_crossings(self, gates, speed_max, *, filter=None, limit=None):
+        """Who walks through each gate within its window, on the device (cs_gate_crossings).  gates: a GATE_DTYPE array
+        (gates_array, path_gates): segments A -> B with a window t0 .. t1 in seconds from now.  Returns (rows, counts):
+        rows a structured array (gate, dir, id, s, u) ascending by (gate, id): agent id crosses gate `gate` at t0 + s at
+        the point A + u * (B - A) and ends on the left (dir +1) or the right (dir -1) of A -> B, if it keeps the velocity
+        it has now; counts (n, 2) uint64, the full number of rows of each gate with dir +1 and with dir -1.  The rule is
+        that of include/crowdstep_state.h ("Who crosses a line"), in f64, bit for bit.  Agents at or above speed_max are
+        not considered.  `filter`: a selection (a dict of select_agents' terms, or a Selection) or None for everyone.
+        `limit`: at most that many rows (the first ones); None lists all, and above _abi.CS_PAIRS_MAX raises,
+        count_gate_crossings has no limit.  Changes nothing."""
+        fn = state_fn(self._lib, self.backend, "cs_gate_crossings", "gate_crossings")
+        _, counts, rows = gate_crossings_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, gates,
+                                            speed_max, filter, limit)
+        return rows, counts
+
+    def count_gate_crossings(self, gates, speed_max, filter=None):
+        """The number of rows of gate_crossings(...) per gate and direction ((n, 2) uint64: dir +1, dir -1), from one
+        pass that lists nothing, exact whatever its size."""
+        fn = state_fn(self._lib, self.backend, "cs_gate_crossings", "gate_crossings")
+        return gate_crossings_of(fn, self._engine, lambda p: self._planner_handles.get(id(p)), self._err, gates, speed_max,
+                                 filter, 0)[1]
 
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):

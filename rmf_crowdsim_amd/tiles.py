@@ -886,6 +886,22 @@ class NativeTileMesh:
         fn = state_fn(self._lib, "mesh", "cs_mesh_zone_agents", "zone_agents")
         return zone_agents_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, polygons, filter, 0)[1]
 
+    def gate_crossings(self, gates, speed_max, *, filter=None, limit=None):
+        """Simulation.gate_crossings on the mesh (cs_mesh_gate_crossings): the single engine's answer, byte for byte
+        (collective in the distributed form).  Every tile runs all gates against the agents it owns; one gather carries
+        the counts, one more the rows, which every rank merges by (gate, id)."""
+        from .simulation import gate_crossings_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_gate_crossings", "gate_crossings")
+        _, counts, rows = gate_crossings_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, gates, speed_max,
+                                            filter, limit)
+        return rows, counts
+
+    def count_gate_crossings(self, gates, speed_max, filter=None):
+        """Simulation.count_gate_crossings on the mesh (collective in the distributed form): only counts travel."""
+        from .simulation import gate_crossings_of, state_fn
+        fn = state_fn(self._lib, "mesh", "cs_mesh_gate_crossings", "gate_crossings")
+        return gate_crossings_of(fn, self._mesh, lambda p: self._handles.get(id(p)), self._err, gates, speed_max, filter, 0)[1]
+
     def remove_selected(self, selection=None, *, rect=None, circle=None, source_sink=None, high_level_planner=None,
                         local_planner=None, waypoint=None, speed=None):
         """Simulation.remove_selected on the mesh (cs_mesh_remove_selected; collective in the distributed form)."""
