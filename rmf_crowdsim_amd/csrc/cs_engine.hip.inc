@@ -2185,17 +2185,24 @@ struct cs_engine {
       // (CS_DEBUG_CTX_BY_VALUE=1, measurement only: a plain crowd through the instantiation with 146 spilled scalars,
       //  profiles/K4_LEVERS.md round 5)
       const bool ctx_by_value = has_sinks || any_route_hlp || debug_ctx_by_value;
-      auto launch_tiled = [&](hipStream_t s, const StepParams& Pl, const TileCfg& c) {
+      // (windows that stage at most TILE_XF_ROWS rows, owned rows + h on either side, keep x as an exact float: k_step_tiled, XF)
+      const bool x_float = rb + 2u * (uint32_t)h <= (uint32_t)TILE_XF_ROWS;
+      auto launch_tiled_as = [&](auto xf_tag, hipStream_t s, const StepParams& Pl, const TileCfg& c) {
+        constexpr bool XF = decltype(xf_tag)::value;
         const dim3 grid(grid_blocks + builders), block(TILE_THREADS);
         const EpilogueCore& Ec = static_cast<const EpilogueCore&>(E);
         if (ctx_by_value && builders)
-          hipLaunchKernelGGL((k_step_tiled<true, true>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
+          hipLaunchKernelGGL((k_step_tiled<true, true, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
         else if (ctx_by_value)
-          hipLaunchKernelGGL((k_step_tiled<true, false>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
+          hipLaunchKernelGGL((k_step_tiled<true, false, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
         else if (builders)
-          hipLaunchKernelGGL((k_step_tiled<false, true>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
+          hipLaunchKernelGGL((k_step_tiled<false, true, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
         else
-          hipLaunchKernelGGL((k_step_tiled<false, false>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
+          hipLaunchKernelGGL((k_step_tiled<false, false, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
+      };
+      auto launch_tiled = [&](hipStream_t s, const StepParams& Pl, const TileCfg& c) {
+        if (x_float) launch_tiled_as(std::true_type{}, s, Pl, c);
+        else launch_tiled_as(std::false_type{}, s, Pl, c);
       };
       if (check_windows && n_slots && rb > 1 && !split)
         if (int rc = check_window_list(blk_desc, n_blocks_dev, rb, n_bands, tile_max_cols((uint32_t)h), want_keep, grid_blocks)) return rc;
@@ -2217,8 +2224,12 @@ struct cs_engine {
         {
           const dim3 grid(grid_blocks), block(TILE_THREADS);  // (no builder workgroups: kept windows and a split exclude each other)
           const EpilogueCore& Ec = static_cast<const EpilogueCore&>(E);
-          if (ctx_by_value)
+          if (ctx_by_value && x_float)
+            hipLaunchKernelGGL((k_step_tiled<true, false, true, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c2);
+          else if (ctx_by_value)
             hipLaunchKernelGGL((k_step_tiled<true, false, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c2);
+          else if (x_float)
+            hipLaunchKernelGGL((k_step_tiled<false, false, true, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c2);
           else
             hipLaunchKernelGGL((k_step_tiled<false, false, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c2);
         }

@@ -711,7 +711,17 @@ struct TileCfg {
 // EARLY = true: the early-exchange form of CS_CFG_TILE_OVERLAP (TileCfg::split == 2: one launch over both window lists, the
 // border windows first, counting themselves off).  An instantiation of its own for the reason WITH_BUILDERS is one: with
 // the code merely present the plain kernel lost 1.1 % at 1M agents (profiles/r05/variants_early.txt).
-template <bool CTX_BY_VALUE, bool WITH_BUILDERS, bool EARLY = false>
+// XF = true: windows that stage at most TILE_XF_ROWS rows (h = 1 with one- or two-row bands, strips: the host's choice,
+// cs_engine) keep a staged x as the BITS OF A FLOAT.  Such an x is (k - kc) cs_fix + fix_coord with k - kc in [-2, 1] and
+// cs_fix <= 2^23, an integer of magnitude <= 2^24 = TILE_XF_LIM and so exact in f32; for two exact operands the f32
+// difference x_j - x_i is the correctly rounded exact difference, which is what (float)(x_j - x_i) of the integer form is,
+// +0 for equal operands included (tests/test_staged_x_exact.py).  The loops below then form x_j - x_i with one full-rate
+// subtraction where the integer form needs a subtraction and a half-rate conversion.  The range is enforced while placing
+// (s_huge, bit 1): a record beyond it, an agent clamped or aliased outside its cell, sends the window down the gather path for
+// this step.  y runs along the window (up to 2^26 units) and stays an integer.  XF = false is the integer form throughout.
+#define TILE_XF_ROWS 4
+#define TILE_XF_LIM 0x1000000  /* 2^24 */
+template <bool CTX_BY_VALUE, bool WITH_BUILDERS, bool EARLY = false, bool XF = false>
 __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     StepParams P, AgentArrays in, const EpilogueCtx* __restrict__ Ep, EpilogueCore Ev,
     const uint32_t* __restrict__ cell_start, const float2* __restrict__ pref, const BlockDesc* __restrict__ desc,
@@ -809,6 +819,10 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
   __shared__ unsigned short s_self[TILE_THREADS];  // LDS slot of the first chunk's owned agents
   // some staged agent moves at 2^31 m/s or more (the model has thrown it, zanlungo.rs:165-167): the workgroup's
   // time-to-collision passes then take the guarded form, which rescales such pairs (ttc_huge)
+  // XF: bit 1 of the same word (no LDS of its own: the host prices a workgroup's static arrays) says that some staged
+  // record's x lies beyond +-TILE_XF_LIM, so is not exact as a float: the window leaves the LDS path for this step.  Both
+  // bits are set while placing (there with atomicOr, so that neither write loses the other) and read behind the barrier
+  // that ends the staging.
   __shared__ uint32_t s_huge;
   // An agent has left the grid (this step or, with nobody waiting for reports, an earlier one): the step has failed,
   // the engine is poisoned at the next synchronisation, and whatever this launch computed would be thrown away.
@@ -904,7 +918,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
   // (+ 2: an aligned pair of invisible slots behind the tile, where lanes past their run look)
   const bool tiled_ok = S + 2u <= cfg.agents_cap && S < 65533u && (uint32_t)(nr * W1) <= cfg.table_cap &&
                         (long long)(W1 / 2 + 2) * g.cs_fix <= (long long)FIX_LIM &&
-                        (long long)(nr / 2 + 2) * g.cs_fix <= (long long)FIX_LIM;
+                        (long long)(nr / 2 + 2) * g.cs_fix <= (long long)FIX_LIM && (!XF || nr <= TILE_XF_ROWS);
 
   // The first chunk's own agents: their loads do not depend on the tile, so they are issued
   // before the staging round trips and travel together with them.
@@ -954,6 +968,12 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     p.y = ok ? fix_coord(off.y, g) + (cy - cyc) * g.cs_fix : FIX_FAR;
     return p;
   };
+  // the x of a staged slot: XF, the bits of the float (FIX_FAR = 2^30 is exact too); else the integer
+  auto stage_x = [&](int x) {
+    if constexpr (XF) return __float_as_int((float)x);
+    else return x;
+  };
+  const int far_x = stage_x(FIX_FAR);
 
   if (tiled_ok) {
     // Staged agent s of the tile = member (s - s_rc[k]) of staged row k; its id goes to a
@@ -982,10 +1002,18 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
         for (; q < te; ++q) rank += (s_idtmp[q] < idj) ? 1u : 0u;
       }
       const uint32_t slot = tb + rank;
-      s_pos[slot] = window_pos(offj, k, cy);
+      int2 p = window_pos(offj, k, cy);
+      if constexpr (XF) {  // (an agent staged at FIX_FAR is out of everybody's sight in either form)
+        if (p.x != FIX_FAR && (uint32_t)(p.x + TILE_XF_LIM) > 2u * (uint32_t)TILE_XF_LIM) atomicOr(&s_huge, 2u);
+        p.x = stage_x(p.x);
+      }
+      s_pos[slot] = p;
       s_vel[slot] = velj;
       s_id[slot] = idj;
-      if (fmaxf(fabsf(velj.x), fabsf(velj.y)) >= 0.5f * TTC_HUGE_SPEED) s_huge = 1u;
+      if (fmaxf(fabsf(velj.x), fabsf(velj.y)) >= 0.5f * TTC_HUGE_SPEED) {
+        if constexpr (XF) atomicOr(&s_huge, 1u);
+        else s_huge = 1u;
+      }
       note_self(k, gj, slot);
     };
     auto fill_table = [&]() {  // first LDS slot of every staged cell (+ one end marker per row)
@@ -997,7 +1025,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
       }
       if (tid >= TILE_THREADS - 2) {  // the invisible pair behind the tile (slots S, S + 1)
         const uint32_t q = S + (uint32_t)(tid - (TILE_THREADS - 2));
-        s_pos[q] = make_int2(FIX_FAR, FIX_FAR);
+        s_pos[q] = make_int2(far_x, FIX_FAR);
         s_vel[q] = make_float2(0.f, 0.f);
         s_id[q] = 0u;
       }
@@ -1006,7 +1034,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
         const int k = tid >> 1;
         const uint32_t c = s_rc[k + 1] - s_rc[k], q = c + (uint32_t)(tid & 1);
         if (s_base[k] + q < s_base[k + 1]) {
-          s_pos[s_base[k] + q] = make_int2(FIX_FAR, FIX_FAR);
+          s_pos[s_base[k] + q] = make_int2(far_x, FIX_FAR);
           s_vel[s_base[k] + q] = make_float2(0.f, 0.f);
           s_id[s_base[k] + q] = 0u;
         }
@@ -1087,7 +1115,16 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
   __builtin_amdgcn_s_setprio(0);
 
   PHASE_MARK(5);
-  const bool tile_huge = s_huge != 0u;  // (after the barrier that ends the staging)
+  const uint32_t tile_flags = s_huge;  // (after the barrier that ends the staging)
+  const bool tile_huge = XF ? (tile_flags & 1u) != 0u : tile_flags != 0u;
+  // the window's agents take the LDS path (block-uniform); XF: not with a staged x beyond the exact range
+  bool lds_ok = tiled_ok;
+  if constexpr (XF) {
+    if (tiled_ok && (tile_flags & 2u) != 0u) {
+      lds_ok = false;
+      if (tid == 0) atomicAdd(&E.ctr->n_win_off_lds, 1u);
+    }
+  }
   // ---- one thread = one agent; idle lanes keep the wave-uniform loops going.  A window that
   // holds more than TILE_THREADS agents (dense spots) is walked in chunks. ----
   for (uint32_t chunk = 0; chunk < n_own; chunk += TILE_THREADS) {
@@ -1125,7 +1162,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     const float slack = 0.01f * g.cs;
     const bool regular = o.off.x >= -slack && o.off.x <= g.cs + slack && o.off.y >= -slack &&
                          o.off.y <= g.cs + slack;
-    if (tiled_ok && regular && sight_ok) {
+    if (lds_ok && regular && sight_ok) {
       // get_bounds relative to the own cell (cell_bounds with g = 0), in 32-bit integers: the same
       // floors, saturated at +-1e9 cells instead of +-4e9 (an eyesight of any size only matters up
       // to the h cells the tile reaches)
@@ -1149,7 +1186,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     if (tz) atomicAdd(&E.ctr->n_tti_zero, 1u);
   }
 
-  if (tiled_ok && !TILE_DEBUG(1u)) {  // block-uniform; lanes without tile work idle through
+  if (lds_ok && !TILE_DEBUG(1u)) {  // block-uniform; lanes without tile work idle through
     const bool mine = zan && use_tile;
     if (!mine) {
       lx = 1; hx = 0; ly = 1; hy = 0;
@@ -1161,6 +1198,13 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     const int own_row = R - r0;
     const int own_col = (int)o.gy - sy0;
     const int2 pi = window_pos(o.off, own_row, own_col);
+    // x_j - x_i of a staged x in fixed units.  XF: both are exact floats, one subtraction gives the bits of the integer
+    // form's subtraction + conversion (see the template's note); the own x is a staged record's, so within the range.
+    const float pix = (float)pi.x;
+    auto rel_x = [&](int xj) {
+      if constexpr (XF) return __int_as_float(xj) - pix;
+      else return (float)(xj - pi.x);
+    };
     // own LDS slot, to skip self without touching ids
     uint32_t self_slot = 0xFFFFFFFFu;
     if (mine) {
@@ -1193,7 +1237,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     // p_j - p_i of a staged neighbour in fixed units: exact integer difference, one conversion
     auto rel = [&](uint32_t j, float& rpx, float& rpy) {
       const int2 pj = s_pos[j];
-      rpx = (float)(pj.x - pi.x);
+      rpx = rel_x(pj.x);
       rpy = (float)(pj.y - pi.y);
     };
     // pass 2 over the first `n` entries of the list: t_i and the right-of-way mask.
@@ -1219,8 +1263,8 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
         const int2 pj0 = s_pos[j0], pj1 = s_pos[j1];
         const float2 vj0 = s_vel[j0], vj1 = s_vel[j1];
         const uint32_t id0 = s_id[j0], id1 = s_id[j1];
-        const float rpx0 = (float)(pj0.x - pi.x), rpy0 = (float)(pj0.y - pi.y);
-        const float rpx1 = (float)(pj1.x - pi.x), rpy1 = (float)(pj1.y - pi.y);
+        const float rpx0 = rel_x(pj0.x), rpy0 = (float)(pj0.y - pi.y);
+        const float rpx1 = rel_x(pj1.x), rpy1 = (float)(pj1.y - pi.y);
         const float rvx0 = vj0.x - o.v.x, rvy0 = vj0.y - o.v.y, rvx1 = vj1.x - o.v.x, rvy1 = vj1.y - o.v.y;
         const float d20 = __builtin_fmaf(rpx0, rpx0, rpy0 * rpy0), d21 = __builtin_fmaf(rpx1, rpx1, rpy1 * rpy1);
         float t0, t1;
@@ -1284,8 +1328,8 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
             const int2 pj0 = s_pos[j0], pj1 = s_pos[j1];
             const float2 vj0 = s_vel[j0], vj1 = s_vel[j1];
             const uint32_t id0 = s_id[j0], id1 = s_id[j1];
-            const float rpx0 = (float)(pj0.x - pi.x), rpy0 = (float)(pj0.y - pi.y);
-            const float rpx1 = (float)(pj1.x - pi.x), rpy1 = (float)(pj1.y - pi.y);
+            const float rpx0 = rel_x(pj0.x), rpy0 = (float)(pj0.y - pi.y);
+            const float rpx1 = rel_x(pj1.x), rpy1 = (float)(pj1.y - pi.y);
             const float rvx0 = vj0.x - o.v.x, rvy0 = vj0.y - o.v.y, rvx1 = vj1.x - o.v.x, rvy1 = vj1.y - o.v.y;
             const float d20 = __builtin_fmaf(rpx0, rpx0, rpy0 * rpy0), d21 = __builtin_fmaf(rpx1, rpx1, rpy1 * rpy1);
             float t0, t1;
@@ -1499,8 +1543,8 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
                 if ((tid & 63u) == 0u) atomicAdd(&E.ctr->dbg[5], 1u);
 #endif
                 const int4 pp = lds_ld_i4(v ? src : far);  // two candidates: slots ja and ja + 1
-                const float ax = (float)(pp.x - pi.x), ay = (float)(pp.y - pi.y);
-                const float bx = (float)(pp.z - pi.x), by = (float)(pp.w - pi.y);
+                const float ax = rel_x(pp.x), ay = (float)(pp.y - pi.y);
+                const float bx = rel_x(pp.z), by = (float)(pp.w - pi.y);
                 const float sa = sight_margin(ax, ay, nr2), sb = sight_margin(bx, by, nr2);
                 // branch-free append: a rejected entry is overwritten by the next store
                 const uint32_t la = lp;
@@ -1552,8 +1596,8 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
               const int4* __restrict__ src = reinterpret_cast<const int4*>(s_pos + (j0 & ~1u));
               while (__any((int)k < (int)n_run)) {
                 const int4 pp = *src;  // two candidates: slots j0 + k and j0 + k + 1
-                const float ax = (float)(pp.x - pi.x), ay = (float)(pp.y - pi.y);
-                const float bx = (float)(pp.z - pi.x), by = (float)(pp.w - pi.y);
+                const float ax = rel_x(pp.x), ay = (float)(pp.y - pi.y);
+                const float bx = rel_x(pp.z), by = (float)(pp.w - pi.y);
                 bool ta = sight_margin(ax, ay, nr2) < 0.0f && k < n_run;
                 bool tb = sight_margin(bx, by, nr2) < 0.0f && k + 1u < n_run;
                 const uint32_t ja = j0 + k;
@@ -1588,8 +1632,8 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
             const int4* __restrict__ src = reinterpret_cast<const int4*>(s_pos + (j0 & ~1u));
             while (__any((int)k < (int)n_run)) {
               const int4 pp = *src;
-              const float ax = (float)(pp.x - pi.x), ay = (float)(pp.y - pi.y);
-              const float bx = (float)(pp.z - pi.x), by = (float)(pp.w - pi.y);
+              const float ax = rel_x(pp.x), ay = (float)(pp.y - pi.y);
+              const float bx = rel_x(pp.z), by = (float)(pp.w - pi.y);
               const uint32_t ja = j0 + k;
               bool ta = sight_margin(ax, ay, nr2) < 0.0f && ja != self_slot && k < n_run;
               bool tb = sight_margin(bx, by, nr2) < 0.0f && ja + 1u != self_slot && k + 1u < n_run;
@@ -1626,7 +1670,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
         while (__any(j < e)) {
           while (j < e && cnt < CAP) {
             const int2 pj = s_pos[j];
-            const float ax = (float)(pj.x - pi.x), ay = (float)(pj.y - pi.y);
+            const float ax = rel_x(pj.x), ay = (float)(pj.y - pi.y);
             bool take = sight_margin(ax, ay, nr2) < 0.0f && j != self_slot;  // strict `<`, location_hash_2d.rs:251
             if (FORCE && take) take = s_id[j] > o.id;
             if (take) {
