@@ -145,7 +145,7 @@ struct Counters {
   // the border windows had packed, so the engine is poisoned.
   uint32_t border_done, border_flag, n_early_stalled;
 #ifdef CS_TILE_TRIPS  // diagnostic build (tools/trip_counts.sh): per-wave loop trips of the tiled kernel, cs_kernel_stat(100 + i)
-  uint32_t dbg[17];
+  uint32_t dbg[20];
 #endif
 };
 
@@ -261,6 +261,23 @@ __device__ __forceinline__ float ttc_core_c_f32(float rvx, float rvy, float rpx,
 __device__ __forceinline__ float ttc_core_f32(float rvx, float rvy, float rpx, float rpy, float d2,
                                               float R2) {
   return ttc_core_c_f32(rvx, rvy, rpx, rpy, d2 - R2);
+}
+
+// ttc_core_c_f32 up to its discriminant, for a pass that finishes only the pairs whose result can be finite (the lean
+// time-to-collision pass of k_step_tiled; DESIGN.md section 4 has the proof).  The SIGN BIT of the key is set only if
+//   disc < 0   or   disc == 0 and bh == 0,
+// and for exactly these ttc_core_c_f32 returns +inf whatever the 1-ulp v_sqrt_f32 / v_rcp_f32 return: the root of a
+// negative number is NaN, so t0 and t1 are NaN; the root of +-0 is +-0, so t1 = (-bh + root) * ia is +-0 or NaN; either
+// way `t1 > 0` fails.  Same a, bh and disc as there, operation for operation.  s = disc + |bh| is negative only for
+// disc < -|bh| <= 0 and zero only for disc = -|bh| (a +0 then: |bh| is never -0), so s <= 0 implies the above; bits(s) - 1
+// turns "s < 0 or s == +0" into one sign bit (+0 wraps around to 0xFFFFFFFF).  The test is
+// conservative: a pair with -|bh| < disc < 0 is finished although it would come out as +inf.  A NaN counts by its sign
+// bit: with a NaN discriminant the root is NaN and the result +inf like for a negative one.
+__device__ __forceinline__ uint32_t ttc_skip_key(float rvx, float rvy, float rpx, float rpy, float c) {
+  const float a = __builtin_fmaf(rvx, rvx, rvy * rvy);
+  const float bh = __builtin_fmaf(rvx, rpx, rvy * rpy);
+  const float disc = __builtin_fmaf(bh, bh, -(a * c));
+  return __float_as_uint(disc + __builtin_fabsf(bh)) - 1u;
 }
 
 // max(|rvx|, |rvy|) as ordered bits minus one: < TTC_TINY_KEY exactly when 0 < |rv|_max < 1e-12,

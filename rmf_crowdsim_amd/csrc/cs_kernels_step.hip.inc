@@ -1307,18 +1307,38 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     //  * overlapping pairs (the only ones that need the guarded quadratic, ttc_pair_f32) are only looked for
     //    (one v_min3 per pair of entries over the overlap keys); a wave that saw one repeats the pass in the
     //    guarded form.
-    auto run_ttc_lds = [&](uint32_t n) {
+    //  * the tail of the quadratic (v_sqrt, v_rcp, two multiply-subtracts, the selects of ttc_select: more than half an
+    //    entry's cost) is only run for the entries whose result can be finite.  The pass over all entries stops at the
+    //    discriminant and shifts one more sign bit per entry into a second pair of words: set when ttc_core_c_f32
+    //    returns +inf whatever its root and reciprocal come out as (ttc_skip_key: disc < 0, or disc == 0 with bh == 0;
+    //    same velocities, or a miss by more than R, which is most of any list).  A second loop pops the other entries'
+    //    bits one 32-bit word at a time, as forward_terms_vanish does, reads each such entry again and runs the parent
+    //    expressions on the same operands, so the bits are those of the one-pass form; the minimum does not mind
+    //    the order (T is never NaN).  Re-reading an entry costs three times what its tail costs in the one-pass loop
+    //    (35 VALU against 12), and the second loop's trip count is the wave's LARGEST number of entries left, so the split
+    //    pays only below ~0.45 entries left per trip of the first pass (profiles/K4_LEVERS.md: walk 0.21, random 0.44,
+    //    creep 0.67), which is only known once the first pass has been paid for.  The form is therefore chosen per
+    //    wave BEFORE the pass, by what makes entries drop out in numbers: a wave all of whose agents walk at exactly
+    //    their preferred velocity (nobody pushed them in the last step: a crowd in free flow, whose groups share a
+    //    velocity to the bit, rv == 0) takes the split form, every other wave the one-pass loop.  Either form gives
+    //    the same bits, so the choice is one of speed alone.  (Only the pass over a complete list has the split form:
+    //    the two calls that drain a full list in mid-filter are rare and keep the one-pass loop, a third of the code.)
+    auto run_ttc_lds = [&](uint32_t n, auto may_split_tag) {
+      constexpr bool MAY_SPLIT = decltype(may_split_tag)::value;
       if (n & 1u) my_list[n * TILE_THREADS] = my_list[(n - 1u) * TILE_THREADS];  // (row n <= CAP: the spare row at most)
       const float T_in = T;
+      const bool split = MAY_SPLIT && !wave_any(n != 0u && (o.v.x != o.u.x || o.v.y != o.u.y));  // (a NaN velocity: one-pass)
       uint32_t w0 = 0u, w1 = 0u;
+      uint32_t l0 = 0u, l1 = 0u;    // split form, per entry: 1 = its time to collision is +inf, no need to finish it
       uint32_t kmin = 0xFFFFFFFFu;  // smallest overlap key of the pairs: < bits(R2) = some pair overlaps
-      auto pass = [&](auto guarded_tag) {
-        constexpr bool GUARDED = decltype(guarded_tag)::value;
+      auto pass = [&](auto form_tag) {
+        constexpr int FORM = decltype(form_tag)::value;  // 0: the whole quadratic, 1: guarded, 2: up to the discriminant
+        constexpr bool GUARDED = FORM == 1;
         const entry_t* __restrict__ lp = my_list;
         // bottom-tested loops (scalar loop control costs issue time: see the filter), one word of right-of-way
         // bits per 32 entries (k is wave-uniform)
         for (uint32_t kb = 0; kb < 64u; kb += 32u) {
-        uint32_t word = 0u, k = kb;
+        uint32_t word = 0u, lword = 0u, k = kb;
         const uint32_t k_end = min(n, kb + 32u);  // (one per-lane bound, so that the loop's exit is ONE vector test)
         bool v = k < k_end;
         if (wave_any(v)) do {
@@ -1332,45 +1352,94 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
             const float rpx1 = rel_x(pj1.x), rpy1 = (float)(pj1.y - pi.y);
             const float rvx0 = vj0.x - o.v.x, rvy0 = vj0.y - o.v.y, rvx1 = vj1.x - o.v.x, rvy1 = vj1.y - o.v.y;
             const float d20 = __builtin_fmaf(rpx0, rpx0, rpy0 * rpy0), d21 = __builtin_fmaf(rpx1, rpx1, rpy1 * rpy1);
-            float t0, t1;
             if (GUARDED) {
-              t0 = ttc_pair_f32(rvx0, rvy0, rpx0, rpy0, d20, R2);
-              t1 = ttc_pair_f32(rvx1, rvy1, rpx1, rpy1, d21, R2);
+              const float t0 = ttc_pair_f32(rvx0, rvy0, rpx0, rpy0, d20, R2);
+              const float t1 = ttc_pair_f32(rvx1, rvy1, rpx1, rpy1, d21, R2);
+              T = fminf(T, fminf(t0, t1));  // a time to collision is never NaN (ttc_select)
             } else {
               kmin = min(kmin, min(ttc_overlap_key(d20), ttc_overlap_key(d21)));
-              t0 = ttc_core_f32(rvx0, rvy0, rpx0, rpy0, d20, R2);
-              t1 = ttc_core_f32(rvx1, rvy1, rpx1, rpy1, d21, R2);
+              if (FORM == 0) {
+                const float t0 = ttc_core_f32(rvx0, rvy0, rpx0, rpy0, d20, R2);
+                const float t1 = ttc_core_f32(rvx1, rvy1, rpx1, rpy1, d21, R2);
+                T = fminf(T, fminf(t0, t1));
+              } else {  // (leaves T alone)
+                lword = __builtin_amdgcn_alignbit(lword, ttc_skip_key(rvx0, rvy0, rpx0, rpy0, d20 - R2), 31);
+                lword = __builtin_amdgcn_alignbit(lword, ttc_skip_key(rvx1, rvy1, rpx1, rpy1, d21 - R2), 31);
+              }
               word = __builtin_amdgcn_alignbit(word, o.id - id0, 31);
               word = __builtin_amdgcn_alignbit(word, o.id - id1, 31);
             }
-            T = fminf(T, fminf(t0, t1));  // a time to collision is never NaN (ttc_select)
           }
           k += 2u;
           v = k < k_end;
         } while (wave_any(v));
-        if (!GUARDED) {  // (as selects: written as branches the two words end up in scratch memory)
+        if (!GUARDED) {  // (as selects: written as branches the words end up in scratch memory)
           w0 = (kb == 0u) ? word : w0;
           w1 = (kb == 0u) ? w1 : word;
+          if (FORM == 2) {
+            l0 = (kb == 0u) ? lword : l0;
+            l1 = (kb == 0u) ? l1 : lword;
+          }
         }
         if (!wave_any(kb + 32u < n)) break;
         }
       };
-      pass(std::false_type{});
+      if constexpr (MAY_SPLIT) {
+        if (split) pass(std::integral_constant<int, 2>{});
+        else pass(std::integral_constant<int, 0>{});
+      } else {
+        pass(std::integral_constant<int, 0>{});
+      }
 #ifdef CS_TILE_TRIPS
+      if ((tid & 63u) == 0u && split) atomicAdd(&E.ctr->dbg[19], 1u);
       if ((tid & 63u) == 0u && wave_any(kmin < __float_as_uint(R2))) atomicAdd(&E.ctr->dbg[8], 1u);
 #endif
-      if (wave_any(kmin < __float_as_uint(R2)) || tile_huge) {  // (rare) some pair overlaps, or somebody in the tile
-                                                                // has been thrown: the pass again, in the guarded form
-        T = T_in;
-        pass(std::true_type{});
-      }
       // entry k's bit is now bit (entries shifted in - 1 - k) of its word: to bit k (k < 32) / bit k - 32, and
       // only the first n entries count
       const uint32_t n2 = (n + 1u) & ~1u;
       const uint32_t b0 = min(n2, 32u), b1 = n2 > 32u ? n2 - 32u : 0u;
+      const unsigned long long valid = n >= 64u ? ~0ull : ((1ull << n) - 1ull);
+      if (wave_any(kmin < __float_as_uint(R2)) || tile_huge) {  // (rare) some pair overlaps, or somebody in the tile
+                                                                // has been thrown: every entry, in the guarded form
+        T = T_in;
+        pass(std::integral_constant<int, 1>{});
+      } else if (split) {
+        if constexpr (MAY_SPLIT) {
+          // the entries that are left: list row k of the word's 32, read again
+          auto finish = [&](uint32_t w, uint32_t row0) {
+            const entry_t* __restrict__ lp = my_list + row0 * TILE_THREADS;
+            while (w) {
+              const uint32_t k = (uint32_t)__builtin_ctz(w);
+              w &= w - 1u;
+              const uint32_t j = lp[k * TILE_THREADS];
+              const float2 vj = s_vel[j];
+              float rpx, rpy;
+              rel(j, rpx, rpy);
+              const float d2 = __builtin_fmaf(rpx, rpx, rpy * rpy);
+              T = fminf(T, ttc_core_f32(vj.x - o.v.x, vj.y - o.v.y, rpx, rpy, d2, R2));
+            }
+          };
+          const uint32_t live_lo = ~__builtin_bitreverse32(l0 << ((32u - b0) & 31u)) & (uint32_t)valid;
+          const uint32_t live_hi = ~__builtin_bitreverse32(l1 << ((32u - b1) & 31u)) & (uint32_t)(valid >> 32);
+#ifdef CS_TILE_TRIPS
+          {
+            const uint32_t pc = (uint32_t)__popc(live_lo) + (uint32_t)__popc(live_hi);
+            uint32_t t = 0;
+            while (wave_any(t < pc)) ++t;
+            uint32_t sum = pc;
+            for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d);
+            if ((tid & 63u) == 0u) {
+              atomicAdd(&E.ctr->dbg[17], t);
+              atomicAdd(&E.ctr->dbg[18], sum);
+            }
+          }
+#endif
+          finish(live_lo, 0u);
+          if (wave_any(live_hi != 0u)) finish(live_hi, 32u);
+        }
+      }
       uint32_t m_lo = b0 ? __builtin_bitreverse32(w0 << ((32u - b0) & 31u)) : 0u;
       uint32_t m_hi = b1 ? __builtin_bitreverse32(w1 << ((32u - b1) & 31u)) : 0u;
-      const unsigned long long valid = n >= 64u ? ~0ull : ((1ull << n) - 1ull);
       const unsigned long long m = ((((unsigned long long)m_hi) << 32) | m_lo) & valid;
       // neighbours without right of way: only their number matters (and only when t_i = 0)
       n_back += n - (uint32_t)__popcll(m);
@@ -1379,7 +1448,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     };
     // a wave that never went beyond the LDS rows runs the lean form alone; one that did, the lean form over
     // the LDS rows and the general one over the few spilled entries behind them
-    auto run_ttc = [&](uint32_t n) {
+    auto run_ttc = [&](uint32_t n, auto may_split_tag) {
 #ifdef CS_TILE_TRIPS
       {
         uint32_t t = 0;
@@ -1396,7 +1465,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
         if (!spilling) run_ttc_impl(n, 0u, std::false_type{});
         else run_ttc_impl(n, 0u, std::true_type{});
       } else {
-        run_ttc_lds(min(n, CAP));
+        run_ttc_lds(min(n, CAP), may_split_tag);
         if (spilling && wave_any(n > CAP)) run_ttc_impl(n, CAP, std::true_type{});
       }
     };
@@ -1660,7 +1729,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
             if (FORCE) {
               run_force_first(cnt);
             } else {
-              run_ttc(cnt);
+              run_ttc(cnt, std::false_type{});
               flushed = true;
             }
             cnt = 0;
@@ -1683,7 +1752,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
             if (FORCE) {
               run_force_first(cnt);
             } else {
-              run_ttc(cnt);
+              run_ttc(cnt, std::false_type{});
               flushed = true;
             }
             cnt = 0;
@@ -1703,7 +1772,7 @@ __global__ void __launch_bounds__(TILE_THREADS, CS_K4_WAVES) k_step_tiled(
     }
 #endif
     if (TILE_DEBUG(8u)) cnt = 0;
-    run_ttc(cnt);
+    run_ttc(cnt, std::true_type{});
     PHASE_MARK(8);
     if (self_listed) n_back -= 1u;
     const bool tz = (T == 0.0f);

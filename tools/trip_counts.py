@@ -34,7 +34,7 @@ def main():
             sim.step(0.05, report=False)
         sim.synchronize()
         L = sim._lib
-        base = [L.cs_kernel_stat(sim._engine, 100 + i) for i in range(17)]
+        base = [L.cs_kernel_stat(sim._engine, 100 + i) for i in range(20)]
     else:
         crowd = {"hotspots": scenes.hotspot_crowd, "random": scenes.random_crowd}[workload]
         pts, grid, _, group = crowd(n, seed=7, cell_size=2.0)
@@ -43,17 +43,22 @@ def main():
         bench.populate(sim, workload, pts, group, scenes.CREEP_SPEED, Zanlungo(*scenes.METRIC_ZANLUNGO), 2.0)
     L = sim._lib
     if workload != "stream":
-        base = [0] * 17
+        base = [0] * 20
     for _ in range(steps):
         sim.step(0.05)
     sim.synchronize()
-    d = [L.cs_kernel_stat(sim._engine, 100 + i) - base[i] for i in range(17)]
+    d = [L.cs_kernel_stat(sim._engine, 100 + i) - base[i] for i in range(20)]
     waves = max(d[0], 1)
     print(f"{workload} {n} agents, {steps} steps: waves/step {d[0] / steps:.0f}  beyond LDS rows {d[1] / waves:.3f}  "
           f"drained {d[2] / waves:.3f}")
     print(f"  per wave: filter trips {d[5] / waves:.1f}  ttc trips {d[4] / waves:.1f} (entries per lane {d[7] / waves / 64:.1f})  "
           f"force trips {d[3] / waves:.1f} (entries per lane {d[6] / waves / 64:.1f})")
     print(f"  time-to-collision passes repeated in the guarded form: {d[8] / waves:.3f} per wave")
+    # the lean pass finishes (root, reciprocal, case analysis) only the entries its discriminant test leaves (ttc_skip_key)
+    # (in waves all of whose agents walk at their preferred velocity: the split form; the others run the one-pass loop)
+    split = max(d[19], 1)
+    print(f"  time-to-collision in the split form: {d[19] / waves:.4f} of the lean passes; entries finished there "
+          f"{d[18] / split / 64:.2f} per lane, finishing trips per such wave (its largest count) {d[17] / split:.2f}")
     agents, finite = max(d[9], 1), d[10]
     print(f"  agents on the LDS path per step {d[9] / steps:.0f}, with a finite time to collision {finite / agents:.4f}")
     # the force pass's pre-test (zanlungo_forward_vanishes) and the fast path it opens
@@ -76,6 +81,7 @@ def main():
         "filter_trips_per_wave": d[5] / waves, "ttc_trips_per_wave": d[4] / waves, "force_trips_per_wave": d[3] / waves,
         "force_lane_use": (d[6] / waves / 64.0) / max(d[3] / waves, 1e-9),
         "waves_beyond_lds_rows_frac": d[1] / waves,
+        "ttc_split_wave_frac": d[19] / waves, "ttc_finish_trips_per_split_wave": d[17] / max(d[19], 1),
         "force_pretest_lane_frac": d[11] / max(finite, 1), "force_pretest_wave_frac": d[12] / waves,
         "force_pretest_entry_frac": d[13] / max(d[16], 1),
         "force_fast_lane_frac": d[14] / max(finite, 1), "force_fast_wave_frac": d[15] / waves,
