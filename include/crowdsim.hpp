@@ -126,6 +126,15 @@ struct HighLevelPlanner {
     d.remove_agent = [](void* u, uint64_t id) { static_cast<HighLevelPlanner*>(u)->remove_agent_id(id); };
     return d;
   }
+  // how a Simulation / a TiledSimulation registers the planner: by its descriptor, unless the planner has a call of its own
+  virtual uint32_t register_with(cs_engine* e) {
+    cs_hlp_desc d = describe();
+    return cs_register_hlp(e, &d);
+  }
+  virtual uint32_t register_with(cs_mesh* m) {
+    cs_hlp_desc d = describe();
+    return cs_mesh_register_hlp(m, &d);
+  }
 };
 struct StubHighLevelPlan : HighLevelPlanner {  // lib.rs:391-420: Some(default_vel)
   Vec2f default_vel;
@@ -145,6 +154,81 @@ struct IdParityHighLevelPlan : StubHighLevelPlan {  // rmf_crowdsim_viz/src/main
     d.kind = CS_HLP_ID_PARITY;
     return d;
   }
+};
+// A navigation (flow) field: a raster of preferred velocities sampled at the agent's position ON THE DEVICE every step
+// (cs_register_hlp_field, include/crowdstep_state.h: no host call and no wait in a step).  raster: the cs_field_desc of
+// agent_field; vxy: nx * ny pairs (vx, vy), bin (ix, iy) at iy * nx + ix; a NaN bin is a wall.  update() replaces the
+// values in every simulation the planner is registered with (they must still be alive); steps already queued keep the
+// old ones.  get_desired_velocity restates the rule for a host that wants to ask the planner itself (bit for bit the
+// device's when this header is compiled without floating-point contraction).
+struct FieldPlanner : HighLevelPlanner {
+  cs_field_desc raster;
+  uint32_t sampling;
+  std::vector<float> vxy;
+  FieldPlanner(const cs_field_desc& r, std::vector<float> values, uint32_t how = CS_HLP_FIELD_NEAREST)
+      : raster(r), sampling(how), vxy(std::move(values)) {
+    if (vxy.size() != 2 * (std::size_t)r.nx * r.ny) throw std::runtime_error("FieldPlanner: vxy holds nx * ny pairs");
+  }
+  void update(const std::vector<float>& values) {
+    if (values.size() != vxy.size()) throw std::runtime_error("FieldPlanner: update keeps the raster: nx * ny pairs");
+    vxy = values;
+    for (auto& b : engines_)
+      if (cs_hlp_field_update(b.first, b.second, vxy.data()) != 0) throw std::runtime_error(cs_last_error(b.first));
+    for (auto& b : meshes_)
+      if (cs_mesh_hlp_field_update(b.first, b.second, vxy.data()) != 0) throw std::runtime_error(cs_mesh_last_error(b.first));
+  }
+  bool get_desired_velocity(const Agent& a, std::chrono::duration<double>, Vec2f* out) override {
+    const cs_field_desc& d = raster;
+    const double fx = (a.position.x - d.x0) / d.cell_w, fy = (a.position.y - d.y0) / d.cell_h;
+    if (!(0.0 <= fx && fx < (double)d.nx && 0.0 <= fy && fy < (double)d.ny)) return false;
+    const uint32_t ix = (uint32_t)fx, iy = (uint32_t)fy;
+    auto sample = [&](uint32_t i, uint32_t j, int k) { return vxy[2 * ((std::size_t)j * d.nx + i) + k]; };
+    auto nearest = [&]() {
+      const float sx = sample(ix, iy, 0), sy = sample(ix, iy, 1);
+      if (sx != sx || sy != sy) return false;
+      *out = {(double)sx, (double)sy};
+      return true;
+    };
+    if (sampling != CS_HLP_FIELD_BILINEAR) return nearest();
+    auto axis = [](double f, uint32_t n, uint32_t* i0, uint32_t* i1, double* t) {
+      const double ax = f - 0.5;
+      if (ax < 0.0) {
+        *i0 = *i1 = 0u;
+        *t = 0.0;
+        return;
+      }
+      *i0 = (uint32_t)ax;
+      *t = ax - (double)*i0;
+      *i1 = *i0 + 1u < n ? *i0 + 1u : n - 1u;
+    };
+    uint32_t i0, i1, j0, j1;
+    double tx, ty, r[2];
+    axis(fx, d.nx, &i0, &i1, &tx);
+    axis(fy, d.ny, &j0, &j1, &ty);
+    for (int k = 0; k < 2; ++k) {
+      const double c00 = sample(i0, j0, k), c10 = sample(i1, j0, k), c01 = sample(i0, j1, k), c11 = sample(i1, j1, k);
+      if (c00 != c00 || c10 != c10 || c01 != c01 || c11 != c11) return nearest();
+      const double lo = c00 + (c10 - c00) * tx, hi = c01 + (c11 - c01) * tx;
+      r[k] = (double)(float)(lo + (hi - lo) * ty);
+    }
+    *out = {r[0], r[1]};
+    return true;
+  }
+  uint32_t register_with(cs_engine* e) override {
+    const uint32_t h = cs_register_hlp_field(e, &raster, sampling, vxy.data());
+    if (h == UINT32_MAX) throw std::runtime_error(cs_last_error(e));  // (refused: the raster or the sampling)
+    engines_.emplace_back(e, h);
+    return h;
+  }
+  uint32_t register_with(cs_mesh* m) override {
+    const uint32_t h = cs_mesh_register_hlp_field(m, &raster, sampling, vxy.data());
+    if (h != UINT32_MAX) meshes_.emplace_back(m, h);
+    return h;
+  }
+
+ private:
+  std::vector<std::pair<cs_engine*, uint32_t>> engines_;
+  std::vector<std::pair<cs_mesh*, uint32_t>> meshes_;
 };
 // The follower half of RMFPlanner (rmf/mod.rs:195-242): override plan_route (the A* of
 // rmf/mod.rs:160-192 is the host's business); it is asked once per new (start, goal) hash pair,
@@ -730,6 +814,7 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     f.ready = rc == 0;
     return f;
   }
+  cs_engine* handle() { return engine_; }  // (for the calls of the C ABI this mirror does not wrap: cs_kernel_stat, ...)
 
  private:
   template <class P>
@@ -741,10 +826,7 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     keep_.push_back(p);
     return h;
   }
-  uint32_t register_planner(HighLevelPlanner* p) {
-    cs_hlp_desc d = p->describe();
-    return cs_register_hlp(engine_, &d);
-  }
+  uint32_t register_planner(HighLevelPlanner* p) { return p->register_with(engine_); }
   uint32_t register_planner(LocalPlanner* p) { return p->register_with(engine_); }
 
   void after_mutation() {
@@ -1204,10 +1286,7 @@ class TiledSimulation {
     keep_.push_back(p);
     return h;
   }
-  uint32_t register_planner(HighLevelPlanner* p) {
-    cs_hlp_desc d = p->describe();
-    return cs_mesh_register_hlp(mesh_, &d);
-  }
+  uint32_t register_planner(HighLevelPlanner* p) { return p->register_with(mesh_); }
   uint32_t register_planner(LocalPlanner* p) { return p->register_with(mesh_); }
   void refresh() {
     cs_event ev[256];

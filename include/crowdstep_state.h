@@ -775,6 +775,51 @@ size_t cs_gate_crossings(cs_engine*, const cs_gate* gates, size_t n, double spee
 size_t cs_mesh_gate_crossings(cs_mesh*, const cs_gate* gates, size_t n, double speed_max, const cs_selection* filter,
                               uint64_t* out_counts, cs_gate_crossing* out, size_t cap);
 
+/* Flow-field high-level planner ("Flow-field planner"): a raster of preferred velocities that lives on
+ * the device and is sampled there every step, for the planners that are a lookup by position: a distance transform to the
+ * exits, a potential that avoids the density cs_agent_field reports, a lane direction map.  The step stays queued: no
+ * download, no host call, no wait.
+ *   - Handles come from the counter of cs_register_hlp and work wherever a planner handle works (cs_add_agents,
+ *     cs_source_sink_desc.hlp, CS_SEL_HLP).  A field planner takes no targets (cs_set_targets: CS_TARGET_IGNORED), hears of
+ *     no removal and gets no set_target event; a source-sink that names it runs its waypoint and sink tests as ever.
+ *   - The raster is the cs_field_desc of cs_agent_field, bin (ix, iy) at iy * nx + ix, nx * ny <= CS_FIELD_MAX_CELLS; vxy
+ *     holds nx * ny pairs (vx, vy) of f32 in HOST memory and is copied before the call returns.  +-inf samples are
+ *     allowed, NaN samples have a meaning (below).
+ *   - The rule.  The agent is the record cs_read_agents would report at the start of the step; x, y its f64 position.
+ *     Every operation is ONE f64 operation rounded once: no contraction, no reciprocal.
+ *       fx = (x - x0) / cell_w, fy = (y - y0) / cell_h (the expression of cs_agent_field); inside iff
+ *       0 <= fx && fx < nx && 0 <= fy && fy < ny; then ix = (uint32_t)fx, iy = (uint32_t)fy.
+ *       NONE is the preferred velocity (0, 0) (lib.rs:263).  An agent outside the raster, or with a NaN or infinite fx
+ *       or fy, gets NONE.
+ *       CS_HLP_FIELD_NEAREST: s = vxy[iy * nx + ix]; NONE if s.vx or s.vy is NaN, else s exactly.
+ *       CS_HLP_FIELD_BILINEAR (samples sit at bin centres, the edges clamp): ax = fx - 0.5; if ax < 0 then i0 = i1 = 0
+ *       and tx = 0, else i0 = (uint32_t)ax, tx = ax - (double)i0, i1 = min(i0 + 1, nx - 1); the same along y for j0,
+ *       j1, ty.  The four samples c00 = (i0, j0), c10 = (i1, j0), c01 = (i0, j1), c11 = (i1, j1) are widened to f64.  If
+ *       any of their eight components is NaN the answer is the NEAREST answer of the agent's own bin (a NaN bin marks a
+ *       wall, and the agents next to it still move).  Otherwise, per component, a = c00 + (c10 - c00) * tx,
+ *       b = c01 + (c11 - c01) * tx, r = a + (b - a) * ty, and the answer is ((float)r_x, (float)r_y).
+ *     What the step integrates is what a CS_HLP_CALLBACK planner returning the same f64 pair would leave: (float)out.  So
+ *     an engine with a field planner and one whose host planner evaluates this rule step to the same bytes.  (A NaN
+ *     ANSWER, which only infinite samples can give, inf - inf or inf * 0, has no specified sign or payload.)
+ *   - cs_hlp_field_update: new values for the same raster and sampling.  Steps already queued use the old values, the
+ *     next step the new ones; the caller's buffer is copied before the call returns and nothing waits for the device.
+ *   - Refused, nothing registered or changed, the engine usable (registration: UINT32_MAX and cs_last_error says why;
+ *     update: 3): a null pointer, a raster cs_agent_field would refuse, an unknown sampling, an update of a handle that
+ *     is not a field planner.
+ *   - Every tile of a mesh holds the whole field (it is indexed in world coordinates); re-cuts keep it.  On a
+ *     distributed mesh both mesh calls are collective with equal arguments.  cs_device_bytes counts the fields. */
+#define CS_HLP_FIELD 5u                 /* kind of a planner made by cs_register_hlp_field */
+#define CS_HLP_FIELD_NEAREST  0u        /* the sample of the agent's own bin                */
+#define CS_HLP_FIELD_BILINEAR 1u        /* between the four nearest bin centres             */
+#define CS_STAT_HLP_FIELD_LAUNCHES 8u   /* cs_kernel_stat: launches of the field kernel so far */
+#define CS_STAT_HLP_FIELD_NS 9u         /* ... and their device time in ns, by events, in an engine created while
+                                         * CS_HLP_FIELD_TIME=1 was set (measurement; 0 otherwise); reading it waits */
+/* Planner handle, or UINT32_MAX (cs_last_error says why). */
+uint32_t cs_register_hlp_field(cs_engine*, const cs_field_desc* raster, uint32_t sampling, const float* vxy);
+int cs_hlp_field_update(cs_engine*, uint32_t hlp, const float* vxy);
+uint32_t cs_mesh_register_hlp_field(cs_mesh*, const cs_field_desc*, uint32_t sampling, const float* vxy);
+int cs_mesh_hlp_field_update(cs_mesh*, uint32_t hlp, const float* vxy);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,17 +5,17 @@ Host-side mirror of the reference trait surface over the C ABI of the HIP engine
 """
 from ._abi import (CS_CFG_DEFAULT, CS_CFG_DENSE, CS_CFG_FORCE_GATHER, CS_CFG_FORCE_TILED, CS_CFG_WIDE_IDS,
                    CS_WRITE_NEXT_WAYPOINT, CS_WRITE_POSITION, CS_WRITE_VELOCITY)
-from .simulation import (Agent, CrowdGenerator, CrowdSimError, EventListener, HighLevelPlanner,
+from .simulation import (Agent, CrowdGenerator, CrowdSimError, EventListener, FieldPlanner, HighLevelPlanner,
                          IdParityHighLevelPlan, LocalPlanner, LocationHash2D, MonotonicCrowd,
                          NoHighLevelPlan, NoLocalPlan, PoissonCrowd, RouteFollower, SeededPoissonCrowd, Selection,
                          Simulation, SourceSink, SpatialIndex,
-                         StubHighLevelPlan, Zanlungo)
+                         StubHighLevelPlan, Zanlungo, flow_field_to_goals)
 
 __all__ = [
-    "Agent", "CrowdGenerator", "CrowdSimError", "EventListener", "HighLevelPlanner",
+    "Agent", "CrowdGenerator", "CrowdSimError", "EventListener", "FieldPlanner", "HighLevelPlanner",
     "IdParityHighLevelPlan", "LocalPlanner", "LocationHash2D", "MonotonicCrowd",
     "NoHighLevelPlan", "NoLocalPlan", "PoissonCrowd", "RouteFollower", "SeededPoissonCrowd", "Selection", "Simulation",
     "SourceSink", "SpatialIndex",
-    "StubHighLevelPlan", "Zanlungo", "CS_CFG_DEFAULT", "CS_CFG_DENSE", "CS_CFG_FORCE_GATHER",
+    "StubHighLevelPlan", "Zanlungo", "flow_field_to_goals", "CS_CFG_DEFAULT", "CS_CFG_DENSE", "CS_CFG_FORCE_GATHER",
     "CS_CFG_FORCE_TILED", "CS_CFG_WIDE_IDS", "CS_WRITE_NEXT_WAYPOINT", "CS_WRITE_POSITION", "CS_WRITE_VELOCITY",
 ]

@@ -21,6 +21,8 @@ CS_STAT_STEPS_ON_KEPT_WINDOWS = 4
 CS_STAT_RENUMBERINGS = 5
 CS_STAT_RENUMBER_NS = 6
 CS_STAT_WINDOWS_LISTED = 7
+CS_STAT_HLP_FIELD_LAUNCHES = 8  # (include/crowdstep_state.h: launches of the field planners' kernel)
+CS_STAT_HLP_FIELD_NS = 9        # (... and their device time, with CS_HLP_FIELD_TIME=1)
 
 CS_HLP_NONE, CS_HLP_CONSTANT, CS_HLP_ID_PARITY, CS_HLP_CALLBACK, CS_HLP_ROUTE = 0, 1, 2, 3, 4
 CS_ROUTE_MAX_WAYPOINTS = 1023
@@ -256,6 +258,8 @@ CS_TARGET_IGNORED, CS_TARGET_BOOKED, CS_TARGET_PLANNED, CS_TARGET_NO_PATH, CS_TA
 CS_SEL_RECT, CS_SEL_CIRCLE, CS_SEL_SOURCE_SINK, CS_SEL_HLP, CS_SEL_LP, CS_SEL_WAYPOINT, CS_SEL_SPEED = 1, 2, 4, 8, 16, 32, 64
 CS_SELECT_MAX = 1024
 CS_FIELD_MAX_CELLS = 4194304
+CS_HLP_FIELD = 5
+CS_HLP_FIELD_NEAREST, CS_HLP_FIELD_BILINEAR = 0, 1
 CS_PAIRS_MAX = 1 << 26
 CS_NO_NEIGHBOUR = 0xFFFFFFFFFFFFFFFF
 CS_NO_HIT = 0xFFFFFFFFFFFFFFFF
@@ -425,6 +429,10 @@ STATE_SYMBOLS = {
     "cs_mesh_zone_agents": (C.c_size_t, list(_ZONE_AGENTS_ARGS)),
     "cs_gate_crossings": (C.c_size_t, list(_GATE_CROSSINGS_ARGS)),
     "cs_mesh_gate_crossings": (C.c_size_t, list(_GATE_CROSSINGS_ARGS)),
+    "cs_register_hlp_field": (C.c_uint32, [C.c_void_p, C.POINTER(FieldDesc), C.c_uint32, C.POINTER(C.c_float)]),
+    "cs_hlp_field_update": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),
+    "cs_mesh_register_hlp_field": (C.c_uint32, [C.c_void_p, C.POINTER(FieldDesc), C.c_uint32, C.POINTER(C.c_float)]),
+    "cs_mesh_hlp_field_update": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),
 }
 
 

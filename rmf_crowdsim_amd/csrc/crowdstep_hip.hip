@@ -21,6 +21,7 @@
 //   cs_set_targets.hip.inc    sending agents to goals by id, a batch at a time (the same header)
 //   cs_select.hip.inc         selecting, counting and removing agents by region, owner and state (the same header)
 //   cs_field.hip.inc          rasterising the crowd into a grid (the same header)
+//   cs_hlp_field.hip.inc      the flow-field high-level planner: a raster of preferred velocities sampled on the device
 //   cs_near.hip.inc           what the four distance queries below share: the walk over the cells in reach, the band of
 //                             a tile, the cross loop over the bands of other tiles, the block helpers, the sort of a list
 //   cs_close_pairs.hip.inc    the pairs of agents within a distance of one another (the same header)
@@ -114,6 +115,7 @@ void cs_destroy(cs_engine* e) {
     hipEventDestroy(e->ev_sorted); hipEventDestroy(e->ev_border); hipEventDestroy(e->ev_xchg);
   }
   hipFree(e->route_desc_dev); hipFree(e->route_xy_dev); hipFree(e->route_book_dev); hipFree(e->hlp_scale_dev); hipFree(e->route_pending_dev);
+  e->free_hlp_fields();
   hipFree(e->groups_dev); hipFree(e->sinks_dev); hipFree(e->waypoints_dev);
   hipFree(e->src_cell_start); hipFree(e->src_sorted); hipFree(e->src_occupied);
   hipFree(e->want_dev); hipFree(e->spawned_slots_dev); hipFree(e->spawn_scratch); hipHostFree(e->want_host); hipFree(e->blk_desc); hipFree(e->blk_desc_back); hipFree(e->n_blocks_dev); hipFree(e->n_blocks_back); hipFree(e->band_prefix); hipFree(e->tile_spill); hipFree(e->spawn_rec_dev); hipFree(e->find_dev); hipFree(e->step_flags_dev); hipFree(e->query_scratch); hipFree(e->scan_tile_sums); hipFree(e->write_scratch); hipFree(e->sel_groups_dev); hipFree(e->field_scratch); hipFree(e->pairs_scratch);
@@ -216,6 +218,7 @@ cs_engine* cs_create(const cs_grid_desc* grid, const cs_device_cfg* cfg) {
   if (const char* v = getenv("CS_OVERLAP_MODE")) e->overlap_early = v[0] != 's';  // "split": rounds 2-4's two launches
   if (const char* v = getenv("CS_DEBUG_CTX_BY_VALUE")) e->debug_ctx_by_value = atoi(v) != 0;  // (measurement only)
   if (const char* v = getenv("CS_DEBUG_SORT_EVERY")) e->debug_sort_every = (uint32_t)std::max(0, atoi(v));  // (measurement only)
+  if (const char* v = getenv("CS_HLP_FIELD_TIME")) e->hlp_field_timing = atoi(v) != 0;  // (measurement only)
   if (const char* v = getenv("CS_TILE_STAGE_CAP")) e->tile_stage_cap = (uint32_t)atoi(v);
   if (const char* v = getenv("CS_TILE_WINDOWS_CAP")) e->tile_windows_cap = (uint32_t)atoi(v);
   if (const char* v = getenv("CS_CHECK_WINDOWS")) e->check_windows = atoi(v) != 0;
@@ -385,6 +388,8 @@ uint64_t cs_kernel_stat(cs_engine* e, uint32_t which) {
   if (which == CS_STAT_STEPS_ON_KEPT_WINDOWS) return e->n_steps_on_kept_windows;
   if (which == CS_STAT_RENUMBERINGS) return e->n_renumberings;
   if (which == CS_STAT_RENUMBER_NS) return e->renumber_ns;
+  if (which == CS_STAT_HLP_FIELD_LAUNCHES) return e->n_hlp_field_launches;
+  if (which == CS_STAT_HLP_FIELD_NS) return e->hlp_field_time_read();
   if (which == CS_STAT_WINDOWS_LISTED) {
     uint64_t n = 0;
     return e->windows_listed(&n) ? 0 : n;
@@ -1306,6 +1311,7 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_set_targets.hip.inc"
 #include "cs_select.hip.inc"
 #include "cs_field.hip.inc"
+#include "cs_hlp_field.hip.inc"
 #include "cs_near.hip.inc"
 #include "cs_close_pairs.hip.inc"
 #include "cs_clusters.hip.inc"

@@ -50,6 +50,24 @@ struct HostGroup {
   int32_t sink;
 };
 
+// CS_HLP_FIELD (cs_hlp_field.hip.inc): one entry per planner handle of the device table k_hlp_field reads; vxy == null:
+// the planner is no field
+struct HlpFieldDev {
+  cs_field_desc d;
+  const float2* vxy;
+  uint32_t sampling, pad;
+};
+// ... and what the host keeps of a field planner: its samples on the device, and a pinned copy of the caller's buffer of
+// the last cs_hlp_field_update with the event behind its upload (the next update waits for that one copy only)
+struct HostHlpField {
+  cs_field_desc d;
+  uint32_t sampling = 0;
+  float2* data = nullptr;
+  float2* stage = nullptr;
+  hipEvent_t staged = nullptr;
+  bool stage_busy = false;
+};
+
 }  // namespace
 
 #define HIP_OK(call)                                                                          \
@@ -65,6 +83,8 @@ struct cs_engine;
 struct StepParams;
 // the host LocalPlanners' turn in a step (crowdstep_hip.hip, next to the batch spatial queries it uses)
 static int lp_callbacks_eval(cs_engine* e, const StepParams& P, const EpilogueCtx* Ep);
+// the field planners' turn in a step: k_hlp_field fills `pref` for their agents (cs_hlp_field.hip.inc)
+static int hlp_field_eval(cs_engine* e);
 
 struct cs_engine {
   // grid (LocationHash2D::new, location_hash_2d.rs:33-51)
@@ -290,6 +310,53 @@ struct cs_engine {
   bool any_callback_hlp = false;        // a planner needs set_target / remove events on the host
   bool any_velocity_callback = false;   // a planner is asked for velocities on the host each step
   bool any_route_hlp = false;
+  // CS_HLP_FIELD (cs_hlp_field.hip.inc).  On the device a field planner's groups are CS_HLP_CALLBACK groups: the step
+  // kernels read pref[i], which k_hlp_field has filled; on the host the planner is a kind of its own and sets none of the
+  // flags above.
+  std::map<uint32_t, HostHlpField> hlp_fields;  // by planner handle
+  HlpFieldDev* hlp_field_tab = nullptr;         // device, one entry per planner handle
+  size_t hlp_field_tab_cap = 0;
+  uint32_t hlp_field_tab_n = 0;                 // entries of it that were uploaded
+  bool hlp_fields_dirty = false;     // a field was registered since the table was uploaded
+  bool any_field_hlp = false;        // some group's planner is a field: k_hlp_field runs every step
+  bool any_silent_callback = false;  // some group's planner is a CS_HLP_CALLBACK without a velocity function (None: its
+                                     // slots of pref must read zero, which nothing but k_hlp_field could have changed)
+  uint64_t n_hlp_field_launches = 0;  // (CS_STAT_HLP_FIELD_LAUNCHES)
+  // CS_HLP_FIELD_TIME=1 (measurement: tools/hlp_field_bench.py): an event either side of every launch of k_hlp_field,
+  // read and added up by cs_kernel_stat(CS_STAT_HLP_FIELD_NS); at most 4,096 pairs wait to be read
+  bool hlp_field_timing = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> hlp_field_timed;
+  uint64_t hlp_field_ns = 0;
+  uint64_t hlp_field_time_read() {
+    for (auto& p : hlp_field_timed) {
+      float ms = 0.0f;
+      if (hipEventSynchronize(p.second) == hipSuccess && hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess)
+        hlp_field_ns += (uint64_t)((double)ms * 1e6);
+      hipEventDestroy(p.first);
+      hipEventDestroy(p.second);
+    }
+    hlp_field_timed.clear();
+    return hlp_field_ns;
+  }
+  uint64_t hlp_field_bytes() const {
+    uint64_t b = hlp_field_tab_cap * sizeof(HlpFieldDev);
+    for (const auto& kv : hlp_fields) b += (uint64_t)kv.second.d.nx * kv.second.d.ny * sizeof(float2);
+    return b;
+  }
+  void free_hlp_fields() {
+    hlp_field_time_read();
+    for (auto& kv : hlp_fields) {
+      if (kv.second.stage_busy) hipEventSynchronize(kv.second.staged);
+      hipFree(kv.second.data);
+      if (kv.second.stage) hipHostFree(kv.second.stage);
+      if (kv.second.staged) hipEventDestroy(kv.second.staged);
+    }
+    hlp_fields.clear();
+    hipFree(hlp_field_tab);
+    hlp_field_tab = nullptr;
+    hlp_field_tab_cap = 0;
+    hlp_field_tab_n = 0;
+  }
 
   // CS_HLP_ROUTE: the route book of RMFPlanner (rmf/mod.rs:83-94).  Routes are planned on the host
   // once per (planner, start hash, goal hash) and live on the device as (first waypoint, count)
@@ -717,6 +784,8 @@ struct cs_engine {
     any_velocity_callback = false;
     any_route_hlp = false;
     any_callback_lp = false;
+    any_field_hlp = false;
+    any_silent_callback = false;
     max_eyesight = 0.0;
     for (size_t i = 0; i < groups.size(); ++i) {
       GroupDev& d = g[i];
@@ -740,6 +809,11 @@ struct cs_engine {
       if (h.kind == CS_HLP_CALLBACK) {
         any_callback_hlp = true;
         if (h.velocity) any_velocity_callback = true;
+        else any_silent_callback = true;
+      }
+      if (h.kind == CS_HLP_FIELD) {  // (to the step kernels: a planner whose answers wait in pref)
+        d.hlp_kind = CS_HLP_CALLBACK;
+        any_field_hlp = true;
       }
       if (h.kind == CS_HLP_ROUTE) {
         d.hvx = (float)h.route_speed;
@@ -1970,6 +2044,9 @@ struct cs_engine {
     // ---- HighLevelPlanner callbacks (slow path) ----
     if (any_velocity_callback)
       if (int rc = eval_callback_hlps()) return rc;
+    // ---- field planners: on the device, behind that upload (it writes the whole of pref), nothing waited for ----
+    if (any_field_hlp)
+      if (int rc = hlp_field_eval(this)) return rc;
     if (any_route_hlp)
       if (int rc = flush_route_tables()) return rc;
 
@@ -2426,7 +2503,9 @@ struct cs_engine {
   // waypoint set_target callbacks (lib.rs:325-333) and DESTROYED events in
   // ascending id (lib.rs:378-380, canonical order).
   int finish_destroy_events(const Counters& c) {
-    if (c.n_wp_events) {
+    // (a field planner's groups are CS_HLP_CALLBACK groups to the step kernel, which lists their waypoint advances too:
+    // nobody listens to those, and the scan zeroes the count before the next step appends)
+    if (c.n_wp_events && (any_callback_hlp || any_route_hlp)) {
       uint32_t m = std::min(c.n_wp_events, wp_events_cap);
       std::vector<WpEvent> w(m);
       HIP_OK(hipMemcpy(w.data(), wp_events, m * sizeof(WpEvent), hipMemcpyDeviceToHost));
@@ -2774,6 +2853,7 @@ struct cs_engine {
     b += write_scratch_bytes;  // the batches of the by-id calls (write, read, remove) and the selections' lists
     b += sel_groups_cap * sizeof(SelGroupDev);
     b += field_scratch_bytes;  // the raster of the last cs_agent_field (cs_field.hip.inc)
+    b += hlp_field_bytes();    // the field planners' samples and their table (cs_hlp_field.hip.inc)
     b += pairs_scratch_bytes;  // the kept part of the lists of the distance queries, at most 16 MiB (cs_near.hip.inc)
     return b;
   }

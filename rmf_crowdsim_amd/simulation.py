@@ -301,6 +301,116 @@ class RouteFollower(HighLevelPlanner):
                             _abi.HlpRemoveFn(), None, fp, self.scale, self.arrive, self.speed), [fp]
 
 
+def field_velocity(origin, cell, vectors, bilinear, x, y):
+    """The rule of cs_register_hlp_field (include/crowdstep_state.h, "Flow-field high-level planner") for one agent at
+    (x, y), in numpy f64 with exactly those operations, each rounded once.  vectors: float32 (ny, nx, 2).  -> (vx, vy) as
+    Python floats that hold f32 values, or None."""
+    f64 = np.float64
+    ny, nx = vectors.shape[0], vectors.shape[1]
+    with np.errstate(all="ignore"):
+        fx = (f64(x) - f64(origin[0])) / f64(cell[0])
+        fy = (f64(y) - f64(origin[1])) / f64(cell[1])
+        if not (0.0 <= fx and fx < f64(nx) and 0.0 <= fy and fy < f64(ny)):
+            return None
+        ix, iy = int(fx), int(fy)
+
+        def nearest():
+            s = vectors[iy, ix]
+            if np.isnan(s[0]) or np.isnan(s[1]):
+                return None
+            return float(s[0]), float(s[1])
+
+        if not bilinear:
+            return nearest()
+
+        def axis(f, n):
+            a = f - f64(0.5)
+            if a < 0.0:
+                return 0, 0, f64(0.0)
+            i0 = int(a)
+            return i0, min(i0 + 1, n - 1), a - f64(i0)
+
+        i0, i1, tx = axis(fx, nx)
+        j0, j1, ty = axis(fy, ny)
+        c00, c10 = vectors[j0, i0].astype(f64), vectors[j0, i1].astype(f64)
+        c01, c11 = vectors[j1, i0].astype(f64), vectors[j1, i1].astype(f64)
+        if np.isnan(c00).any() or np.isnan(c10).any() or np.isnan(c01).any() or np.isnan(c11).any():
+            return nearest()
+        out = []
+        for k in (0, 1):
+            a = c00[k] + (c10[k] - c00[k]) * tx
+            b = c01[k] + (c11[k] - c01[k]) * tx
+            out.append(float(np.float32(a + (b - a) * ty)))
+        return out[0], out[1]
+
+
+class FieldPlanner(HighLevelPlanner):
+    """A navigation (flow) field: a raster of preferred velocities sampled at the agent's position, on the device
+    (cs_register_hlp_field: no host call, no wait in a step).  origin: (x0, y0) of bin (0, 0); cell: a bin size, a scalar
+    or (w, h); vectors: (ny, nx, 2) preferred velocities, stored as f32; sampling: "nearest" (the agent's own bin) or
+    "bilinear" (between the four nearest bin centres, clamped at the edges).  A NaN bin is a wall: None under "nearest",
+    and "bilinear" falls back to the agent's own bin next to one.  Outside the raster: None.  The field takes no
+    targets.
+
+    `get_desired_velocity` is the same rule in numpy f64, so on a library without the call (the test oracle) the planner
+    registers as a plain host planner, and `as_host_planner()` does so everywhere: the comparison the device path is
+    checked against bit for bit."""
+
+    def __init__(self, origin, cell, vectors, sampling="nearest"):
+        if sampling not in ("nearest", "bilinear"):
+            raise CrowdSimError('FieldPlanner: sampling is "nearest" or "bilinear"')
+        self.origin = (float(origin[0]), float(origin[1]))
+        cell = np.asarray(cell, dtype=np.float64).reshape(-1)
+        if len(cell) not in (1, 2):
+            raise CrowdSimError("FieldPlanner: cell is a scalar or a pair (w, h)")
+        self.cell = (float(cell[0]), float(cell[-1]))
+        self.sampling = sampling
+        self.vectors = self._checked(vectors, None)
+        self._bound = []  # (lib or mesh registrar, engine or mesh, planner handle) of every device registration
+
+    @staticmethod
+    def _checked(vectors, shape):
+        v = np.ascontiguousarray(np.asarray(vectors, dtype=np.float32))
+        if v.ndim != 3 or v.shape[2] != 2 or (shape is not None and v.shape != shape):
+            raise CrowdSimError("FieldPlanner: vectors has shape (ny, nx, 2)" + (" of the registered raster" if shape else ""))
+        return v.copy()
+
+    def update(self, vectors):
+        """New values for the same raster.  Steps already queued use the old ones; nothing waits for the device."""
+        self.vectors = self._checked(vectors, self.vectors.shape)
+        for lib, engine, handle in self._bound:
+            if lib.cs_hlp_field_update(engine, handle, self.vectors.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+                raise CrowdSimError(lib.cs_last_error(engine).decode())
+
+    def get_desired_velocity(self, agent, time):
+        return field_velocity(self.origin, self.cell, self.vectors, self.sampling == "bilinear", agent.position[0],
+                              agent.position[1])
+
+    def as_host_planner(self):
+        """The same field as a planner that always takes the host callback path (it follows `update`)."""
+        return _HostFieldPlanner(self)
+
+    def _register(self, lib, engine):
+        try:
+            register = lib.cs_register_hlp_field
+        except AttributeError:  # a library without the call: the plain callback descriptor
+            return HighLevelPlanner._register(self, lib, engine)
+        desc = field_desc(self.origin, self.cell, self.vectors.shape[:2])
+        sampling = _abi.CS_HLP_FIELD_BILINEAR if self.sampling == "bilinear" else _abi.CS_HLP_FIELD_NEAREST
+        handle = register(engine, C.byref(desc), sampling, self.vectors.ctypes.data_as(C.POINTER(C.c_float)))
+        if handle != 0xFFFFFFFF:
+            self._bound.append((lib, engine, handle))
+        return handle
+
+
+class _HostFieldPlanner(HighLevelPlanner):
+    def __init__(self, field):
+        self.field = field
+
+    def get_desired_velocity(self, agent, time):
+        return self.field.get_desired_velocity(agent, time)
+
+
 # ---- source / sink ---------------------------------------------------------
 class CrowdGenerator:
     """trait CrowdGenerator, source_sink.rs:30-33."""
@@ -944,6 +1054,54 @@ def merge_leg_intervals(rows, n_legs):
     offsets = np.zeros(n_legs + 1, dtype=np.int64)
     np.cumsum(np.bincount(leg[begin], minlength=n_legs), out=offsets[1:])
     return offsets, spans
+
+
+def flow_field_to_goals(blocked, goals, origin, cell, speed, return_distance=False):
+    """Vectors for a FieldPlanner(origin, cell, vectors) that lead to the nearest goal around the blocked bins.  blocked,
+    goals: bool (ny, nx).  An 8-connected Dijkstra from the goal bins over the free ones (a step costs the distance between
+    the bin centres; a diagonal step needs both bins beside it free, so nobody cuts a wall's corner); every free bin gets
+    `speed` times the unit vector to the neighbour through which its path is cheapest, a goal bin gets zero, blocked and
+    unreachable bins get NaN.  -> float32 (ny, nx, 2), with return_distance also the path lengths, float64 (ny, nx), inf
+    where no path exists.  Pure numpy and a heap; for examples and benchmarks, it claims no optimality.  (The origin does
+    not enter the vectors; it is taken so that the call reads like the planner's.)"""
+    import heapq
+    blocked = np.asarray(blocked, dtype=bool)
+    goals = np.asarray(goals, dtype=bool)
+    if blocked.ndim != 2 or goals.shape != blocked.shape:
+        raise ValueError("flow_field_to_goals: blocked and goals are bool arrays of one shape (ny, nx)")
+    float(origin[0]), float(origin[1])
+    cell = np.asarray(cell, dtype=np.float64).reshape(-1)
+    cw, ch = float(cell[0]), float(cell[-1])
+    ny, nx = blocked.shape
+    dist = np.full((ny, nx), np.inf)
+    via = np.zeros((ny, nx, 2), dtype=np.int64)  # the step (dx, dy) towards the goal
+    heap = []
+    for iy, ix in zip(*np.nonzero(goals & ~blocked)):
+        dist[iy, ix] = 0.0
+        heap.append((0.0, int(iy), int(ix)))
+    heapq.heapify(heap)
+    steps = [(dx, dy, float(np.hypot(dx * cw, dy * ch))) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if dx or dy]
+    while heap:
+        d, iy, ix = heapq.heappop(heap)
+        if d > dist[iy, ix]:
+            continue
+        for dx, dy, cost in steps:
+            jx, jy = ix + dx, iy + dy
+            if not (0 <= jx < nx and 0 <= jy < ny) or blocked[jy, jx]:
+                continue
+            if dx and dy and (blocked[iy, jx] or blocked[jy, ix]):
+                continue
+            if d + cost < dist[jy, jx]:
+                dist[jy, jx] = d + cost
+                via[jy, jx] = (-dx, -dy)
+                heapq.heappush(heap, (d + cost, jy, jx))
+    out = np.full((ny, nx, 2), np.nan, dtype=np.float32)
+    reached = np.isfinite(dist)
+    step = via[reached].astype(np.float64) * (cw, ch)
+    norm = np.hypot(step[:, 0], step[:, 1])
+    norm[norm == 0.0] = 1.0  # (the goal bins: a zero vector)
+    out[reached] = (float(speed) * step / norm[:, None]).astype(np.float32)
+    return (out, dist) if return_distance else out
 
 
 def free_spans(offsets, spans, t0, t1):

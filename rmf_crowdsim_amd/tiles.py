@@ -149,9 +149,10 @@ def halo_capacity_of(layout, tx, ty, direction, density_per_cell, halo_cells, sl
 
 def _is_data_planner(source_sink):
     """True when the sink's high-level planner runs on the device without host events.  A route
-    follower on a tile qualifies: its routes are planned when the sink is registered."""
-    from .simulation import RouteFollower, _DataPlan
-    return isinstance(source_sink.high_level_planner, (_DataPlan, RouteFollower))
+    follower on a tile qualifies: its routes are planned when the sink is registered.  So does a field planner: its
+    raster lives on every tile's device."""
+    from .simulation import FieldPlanner, RouteFollower, _DataPlan
+    return isinstance(source_sink.high_level_planner, (_DataPlan, RouteFollower, FieldPlanner))
 
 
 def _has_route_legs(source_sink):
@@ -393,6 +394,8 @@ class _MeshRegistrar:
     def __getattr__(self, name):
         if name.startswith("cs_register_") and hasattr(self._lib, "cs_mesh_register_" + name[len("cs_register_"):]):
             return getattr(self._lib, "cs_mesh_register_" + name[len("cs_register_"):])
+        if name == "cs_hlp_field_update" and hasattr(self._lib, "cs_mesh_hlp_field_update"):  # (FieldPlanner.update)
+            return self._lib.cs_mesh_hlp_field_update
         if name == "cs_last_error":
             return self._lib.cs_mesh_last_error
         raise AttributeError(f"{name}: not available on a mesh")
