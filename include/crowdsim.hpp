@@ -155,6 +155,55 @@ struct IdParityHighLevelPlan : StubHighLevelPlan {  // rmf_crowdsim_viz/src/main
     return d;
   }
 };
+// One flow-field solve (cs_flow_field_solve, include/crowdstep_state.h, "Solving a flow field on the device"): goals and
+// blocked hold nx * ny bytes (blocked may be empty: no walls), slowness nx * ny floats (empty: 1 everywhere), bin (ix, iy)
+// at iy * nx + ix.  A step out of a bin costs its length times slowness * (1 + density_weight * the agents in the bin).
+struct FlowProblem {
+  cs_field_desc raster{};
+  std::vector<uint8_t> goals, blocked;
+  std::vector<float> slowness;
+  double speed = 1.0, density_weight = 0.0;
+  const cs_selection* density_filter = nullptr;
+  cs_flow_desc desc() const {
+    const std::size_t bins = (std::size_t)raster.nx * raster.ny;
+    if (goals.size() != bins || (!blocked.empty() && blocked.size() != bins) || (!slowness.empty() && slowness.size() != bins))
+      throw std::runtime_error("FlowProblem: goals, blocked and slowness hold nx * ny values (or none)");
+    cs_flow_desc d{};
+    d.raster = raster;
+    d.goals = goals.data();
+    d.blocked = blocked.empty() ? nullptr : blocked.data();
+    d.slowness = slowness.empty() ? nullptr : slowness.data();
+    d.speed = speed;
+    d.density_weight = density_weight;
+    d.density_filter = density_filter;
+    return d;
+  }
+};
+// ... and what it returns: the vectors (nx * ny pairs; NaN at blocked and unreachable bins) and the distances (+inf there),
+// each empty unless asked for; the bins with a path to a goal; the rounds the device ran.
+struct FlowField {
+  uint32_t nx = 0, ny = 0;
+  std::vector<float> vxy;
+  std::vector<double> dist;
+  uint64_t reached = 0;
+  uint32_t rounds = 0;
+};
+template <class Handle, class Call, class Why>
+inline FlowField flow_solve_call(Handle* h, Call call, Why why, const FlowProblem& p, uint32_t hlp, bool vectors, bool distance) {
+  const cs_flow_desc d = p.desc();
+  FlowField f;
+  f.nx = p.raster.nx;
+  f.ny = p.raster.ny;
+  const std::size_t bins = (std::size_t)f.nx * f.ny;
+  if (vectors) f.vxy.assign(2 * bins, 0.0f);
+  if (distance) f.dist.assign(bins, 0.0);
+  cs_flow_stats st{};
+  if (call(h, &d, hlp, vectors ? f.vxy.data() : nullptr, distance ? f.dist.data() : nullptr, &st) != 0)
+    throw std::runtime_error(why(h));
+  f.reached = st.reached;
+  f.rounds = st.rounds;
+  return f;
+}
 // A navigation (flow) field: a raster of preferred velocities sampled at the agent's position ON THE DEVICE every step
 // (cs_register_hlp_field, include/crowdstep_state.h: no host call and no wait in a step).  raster: the cs_field_desc of
 // agent_field; vxy: nx * ny pairs (vx, vy), bin (ix, iy) at iy * nx + ix; a NaN bin is a wall.  update() replaces the
@@ -176,6 +225,28 @@ struct FieldPlanner : HighLevelPlanner {
       if (cs_hlp_field_update(b.first, b.second, vxy.data()) != 0) throw std::runtime_error(cs_last_error(b.first));
     for (auto& b : meshes_)
       if (cs_mesh_hlp_field_update(b.first, b.second, vxy.data()) != 0) throw std::runtime_error(cs_mesh_last_error(b.first));
+  }
+  // Solve the flow field of `p` (whose raster is this planner's) on the device and write it into this planner's samples
+  // in every simulation it is registered with: behind the steps already queued, in front of the next.  With vectors and
+  // distance both false no raster crosses the bus.  The host's copy `vxy` follows when the vectors are asked for.
+  FlowField solve(const FlowProblem& p, bool vectors = true, bool distance = false) {
+    if (engines_.empty() && meshes_.empty()) throw std::runtime_error("FieldPlanner::solve: registered with no simulation yet");
+    FlowField f;
+    for (auto& b : engines_) f = flow_solve_call(b.first, cs_flow_field_solve, cs_last_error, p, b.second, vectors, distance);
+    for (auto& b : meshes_) f = flow_solve_call(b.first, cs_mesh_flow_field_solve, cs_mesh_last_error, p, b.second, vectors, distance);
+    if (vectors) vxy = f.vxy;
+    return f;
+  }
+  // this planner's handle in an engine or a mesh, UINT32_MAX where it is not registered
+  uint32_t handle_in(const cs_engine* e) const {
+    for (auto& b : engines_)
+      if (b.first == e) return b.second;
+    return UINT32_MAX;
+  }
+  uint32_t handle_in(const cs_mesh* m) const {
+    for (auto& b : meshes_)
+      if (b.first == m) return b.second;
+    return UINT32_MAX;
   }
   bool get_desired_velocity(const Agent& a, std::chrono::duration<double>, Vec2f* out) override {
     const cs_field_desc& d = raster;
@@ -546,6 +617,17 @@ class Simulation {  // Simulation<LocationHash2D>, lib.rs:69-383
     if (cs_agent_field(engine_, &desc, filter, f.count.data(), velocity ? f.sum_vx.data() : nullptr,
         velocity ? f.sum_vy.data() : nullptr) != 0)
       throw std::runtime_error(cs_last_error(engine_));
+    return f;
+  }
+  // Solve a flow field on the device (FlowProblem; include/crowdstep_state.h, "Solving a flow field on the device").
+  // `planner`: a FieldPlanner of the problem's raster registered here, whose device samples take the vectors behind the
+  // steps already queued.  The call waits for the device.
+  FlowField solve_flow_field(const FlowProblem& p, FieldPlanner* planner = nullptr, bool vectors = true, bool distance = false) {
+    uint32_t hlp = UINT32_MAX;
+    if (planner && (hlp = planner->handle_in(engine_)) == UINT32_MAX)
+      throw std::runtime_error("solve_flow_field: the planner is not registered with this simulation");
+    FlowField f = flow_solve_call(engine_, cs_flow_field_solve, cs_last_error, p, hlp, vectors, distance);
+    if (planner && vectors) planner->vxy = f.vxy;
     return f;
   }
   // The pairs of agents closer than `distance` on the device (include/crowdstep_state.h, "Pairs of agents between
@@ -1024,6 +1106,17 @@ class TiledSimulation {
     if (cs_mesh_agent_field(mesh_, &desc, filter, f.count.data(), velocity ? f.sum_vx.data() : nullptr,
         velocity ? f.sum_vy.data() : nullptr) != 0)
       throw std::runtime_error(cs_mesh_last_error(mesh_));
+    return f;
+  }
+  // Solve a flow field on the device (FlowProblem; include/crowdstep_state.h, "Solving a flow field on the device").
+  // `planner`: a FieldPlanner of the problem's raster registered here, whose device samples take the vectors behind the
+  // steps already queued.  The call waits for the device.
+  FlowField solve_flow_field(const FlowProblem& p, FieldPlanner* planner = nullptr, bool vectors = true, bool distance = false) {
+    uint32_t hlp = UINT32_MAX;
+    if (planner && (hlp = planner->handle_in(mesh_)) == UINT32_MAX)
+      throw std::runtime_error("solve_flow_field: the planner is not registered with this simulation");
+    FlowField f = flow_solve_call(mesh_, cs_mesh_flow_field_solve, cs_mesh_last_error, p, hlp, vectors, distance);
+    if (planner && vectors) planner->vxy = f.vxy;
     return f;
   }
   // The pairs of agents closer than `distance` on the device (include/crowdstep_state.h, "Pairs of agents between

@@ -820,6 +820,62 @@ int cs_hlp_field_update(cs_engine*, uint32_t hlp, const float* vxy);
 uint32_t cs_mesh_register_hlp_field(cs_mesh*, const cs_field_desc*, uint32_t sampling, const float* vxy);
 int cs_mesh_hlp_field_update(cs_mesh*, uint32_t hlp, const float* vxy);
 
+/* Solving a flow field on the device ("Solving a flow field"): from goal bins, walls, a slowness
+ * raster and the crowd's density to the raster of preferred velocities a field planner samples, without a host solve and
+ * without the raster crossing the bus.  The distances are shortest-path distances by a rule of single IEEE operations,
+ * so they are the same f64 bits whatever order the relaxations run in: a host Dijkstra, sweeps, tiles on the device.
+ *   - Inputs.  raster: a cs_field_desc (the checks of cs_agent_field), bin (ix, iy) at iy * nx + ix.  goals: uint8_t
+ *     [nx * ny], required, non-zero = a goal.  blocked: uint8_t[nx * ny] or NULL (no walls), non-zero = a wall.
+ *     slowness: float[nx * ny] or NULL (1 everywhere), every value finite and >= 0.  speed: finite, >= 0.
+ *     density_weight: finite, 0 <= w <= 2^32 (so that w * count is finite for any u32 count).  density_filter: a
+ *     cs_selection or NULL (every agent).  All arrays are HOST memory and are read before the call returns.
+ *   - Every operation is ONE f64 operation rounded once: no contraction, no reciprocal, no hypot.
+ *   - Lengths, computed once on the host: len(+-1, 0) = cell_w, len(0, +-1) = cell_h, and for the four diagonals
+ *     len = sqrt(cell_w * cell_w + cell_h * cell_h).
+ *   - Slowness.  s(bin) = (double)slowness[bin] * (1.0 + density_weight * (double)count[bin]), where count is exactly
+ *     what cs_agent_field(raster, density_filter) would report now, the agents the index never took included.  With
+ *     density_weight == 0 no raster of the crowd is made and the factor is left out: s = (double)slowness[bin], or
+ *     exactly 1.0 without a slowness.
+ *   - Moves.  The eight steps (dx, dy) are ordered dy = -1, 0, 1 outer and dx = -1, 0, 1 inner, (0, 0) skipped.  A step
+ *     from (ix, iy) to (ix + dx, iy + dy) is allowed when the target is inside the raster, the target is not blocked,
+ *     and, for a diagonal, neither (ix + dx, iy) nor (ix, iy + dy) is blocked (nobody cuts a wall's corner).  It costs
+ *     len(dx, dy) * s(ix, iy): the slowness of the bin the walker leaves.
+ *   - Distance.  dist = 0 at every bin that is a goal and not blocked, +inf at blocked bins; elsewhere dist(j) = min
+ *     over the allowed steps from j to i of dist(i) + cost.  This is the least fixed point; IEEE addition is monotone
+ *     (a <= b implies a + c <= b + c), so it is unique down to the bits.  Unreachable bins keep +inf.
+ *   - Vector.  A goal bin (not blocked) gets (0, 0).  A blocked or unreachable bin gets (NaN, NaN) (the quiet NaN
+ *     0x7FC00000: a wall to the samplers of cs_register_hlp_field).  Any other bin takes the FIRST step, in the order
+ *     above, whose dist(target) + cost is smallest and finite, and gets ((float)((speed * sx) / n), (float)((speed * sy)
+ *     / n)) with sx = dx * cell_w, sy = dy * cell_h, n = len(dx, dy): eight possible vectors, a table the host makes.
+ *     Where slowness is 0, or where a cost is absorbed by a huge distance (d + c == d), two bins can point at one
+ *     another: the rule promises the distances there, not progress.
+ *   - hlp: a field planner of this engine whose raster equals desc->raster byte for byte, or UINT32_MAX.  With a planner
+ *     the last kernel writes the vectors straight into the planner's device samples on the engine's stream: behind the
+ *     steps already queued, in front of the next one (the ordering of cs_hlp_field_update; an update still in flight is
+ *     ordered by the same stream).  Without out_vxy and out_dist no raster crosses the bus in either direction but the
+ *     masks (and the slowness) going up.
+ *   - The call WAITS for the device: the solve runs in rounds (separate launches, at most nx * ny + 1, a derived bound:
+ *     beyond it the call returns 90) and the host reads one word per round.  What it saves is the host solve and the
+ *     raster's round trips.  stats->reached: the bins with a finite distance; stats->rounds: the rounds launched up to and
+ *     including the first that changed nothing (a measurement: it can differ between two runs, the results cannot).
+ *   - Refused (3), nothing changed anywhere, the planner's samples untouched, the engine usable: a null desc or null
+ *     goals, a raster cs_agent_field would refuse, an hlp that is not a field planner or is one of another raster, a
+ *     slowness that is NaN, infinite or negative, a speed or density_weight outside the ranges above, a selection
+ *     cs_agent_field would refuse, nothing to write to (hlp == UINT32_MAX and both outputs NULL).
+ *   - On a mesh the call is collective with equal arguments.  The counts come by the path of cs_mesh_agent_field (the
+ *     same bytes on every rank); then every tile solves the same problem and writes its own copy of the planner's
+ *     samples.  Outputs are taken from the first local tile.  cs_device_bytes counts the solve's scratch. */
+typedef struct cs_flow_desc {
+  cs_field_desc raster;
+  const uint8_t* goals; const uint8_t* blocked; const float* slowness;
+  double speed, density_weight;
+  const cs_selection* density_filter;
+} cs_flow_desc;
+typedef struct cs_flow_stats { uint64_t reached; uint32_t rounds; uint32_t reserved; } cs_flow_stats;
+/* out_vxy (nx * ny float pairs), out_dist (nx * ny doubles), stats: each may be NULL.  0 = Ok. */
+int cs_flow_field_solve(cs_engine*, const cs_flow_desc*, uint32_t hlp, float* out_vxy, double* out_dist, cs_flow_stats*);
+int cs_mesh_flow_field_solve(cs_mesh*, const cs_flow_desc*, uint32_t hlp, float* out_vxy, double* out_dist, cs_flow_stats*);
+
 #ifdef __cplusplus
 }
 #endif

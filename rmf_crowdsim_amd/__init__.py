@@ -9,13 +9,14 @@ from .simulation import (Agent, CrowdGenerator, CrowdSimError, EventListener, Fi
                          IdParityHighLevelPlan, LocalPlanner, LocationHash2D, MonotonicCrowd,
                          NoHighLevelPlan, NoLocalPlan, PoissonCrowd, RouteFollower, SeededPoissonCrowd, Selection,
                          Simulation, SourceSink, SpatialIndex,
-                         StubHighLevelPlan, Zanlungo, flow_field_to_goals)
+                         StubHighLevelPlan, Zanlungo, flow_field_solve_host, flow_field_to_goals)
 
 __all__ = [
     "Agent", "CrowdGenerator", "CrowdSimError", "EventListener", "FieldPlanner", "HighLevelPlanner",
     "IdParityHighLevelPlan", "LocalPlanner", "LocationHash2D", "MonotonicCrowd",
     "NoHighLevelPlan", "NoLocalPlan", "PoissonCrowd", "RouteFollower", "SeededPoissonCrowd", "Selection", "Simulation",
     "SourceSink", "SpatialIndex",
-    "StubHighLevelPlan", "Zanlungo", "flow_field_to_goals", "CS_CFG_DEFAULT", "CS_CFG_DENSE", "CS_CFG_FORCE_GATHER",
+    "StubHighLevelPlan", "Zanlungo", "flow_field_solve_host", "flow_field_to_goals", "CS_CFG_DEFAULT", "CS_CFG_DENSE",
+    "CS_CFG_FORCE_GATHER",
     "CS_CFG_FORCE_TILED", "CS_CFG_WIDE_IDS", "CS_WRITE_NEXT_WAYPOINT", "CS_WRITE_POSITION", "CS_WRITE_VELOCITY",
 ]

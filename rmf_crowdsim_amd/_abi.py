@@ -284,6 +284,18 @@ class FieldDesc(C.Structure):
                 ("nx", C.c_uint32), ("ny", C.c_uint32)]
 
 
+class FlowDesc(C.Structure):
+    """cs_flow_desc: one flow-field solve (include/crowdstep_state.h, cs_flow_field_solve)"""
+    _fields_ = [("raster", FieldDesc), ("goals", C.POINTER(C.c_uint8)), ("blocked", C.POINTER(C.c_uint8)),
+                ("slowness", C.POINTER(C.c_float)), ("speed", C.c_double), ("density_weight", C.c_double),
+                ("density_filter", C.POINTER(Selection))]
+
+
+class FlowStats(C.Structure):
+    """cs_flow_stats: bins with a finite distance, rounds launched"""
+    _fields_ = [("reached", C.c_uint64), ("rounds", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class IdPair(C.Structure):
     """cs_id_pair: one pair of cs_close_pairs, a < b (include/crowdstep_state.h)"""
     _fields_ = [("a", C.c_uint64), ("b", C.c_uint64)]
@@ -385,6 +397,8 @@ _ZONE_AGENTS_ARGS = [C.c_void_p, C.POINTER(Zone), C.c_size_t, C.POINTER(C.c_doub
                      C.POINTER(C.c_uint64), C.POINTER(ZoneAgent), C.c_size_t]
 _GATE_CROSSINGS_ARGS = [C.c_void_p, C.POINTER(Gate), C.c_size_t, C.c_double, C.POINTER(Selection), C.POINTER(C.c_uint64),
                         C.POINTER(GateCrossing), C.c_size_t]
+_FLOW_SOLVE_ARGS = [C.c_void_p, C.POINTER(FlowDesc), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_double),
+                    C.POINTER(FlowStats)]
 _FIELD_ARGS = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(Selection), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
                C.POINTER(C.c_double)]
 
@@ -433,6 +447,8 @@ STATE_SYMBOLS = {
     "cs_hlp_field_update": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),
     "cs_mesh_register_hlp_field": (C.c_uint32, [C.c_void_p, C.POINTER(FieldDesc), C.c_uint32, C.POINTER(C.c_float)]),
     "cs_mesh_hlp_field_update": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),
+    "cs_flow_field_solve": (C.c_int, list(_FLOW_SOLVE_ARGS)),
+    "cs_mesh_flow_field_solve": (C.c_int, list(_FLOW_SOLVE_ARGS)),
 }
 
 

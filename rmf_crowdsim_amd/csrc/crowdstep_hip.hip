@@ -22,6 +22,7 @@
 //   cs_select.hip.inc         selecting, counting and removing agents by region, owner and state (the same header)
 //   cs_field.hip.inc          rasterising the crowd into a grid (the same header)
 //   cs_hlp_field.hip.inc      the flow-field high-level planner: a raster of preferred velocities sampled on the device
+//   cs_flow_solve.hip.inc     solving such a raster on the device: goals, walls, slowness and the crowd's density
 //   cs_near.hip.inc           what the four distance queries below share: the walk over the cells in reach, the band of
 //                             a tile, the cross loop over the bands of other tiles, the block helpers, the sort of a list
 //   cs_close_pairs.hip.inc    the pairs of agents within a distance of one another (the same header)
@@ -118,7 +119,7 @@ void cs_destroy(cs_engine* e) {
   e->free_hlp_fields();
   hipFree(e->groups_dev); hipFree(e->sinks_dev); hipFree(e->waypoints_dev);
   hipFree(e->src_cell_start); hipFree(e->src_sorted); hipFree(e->src_occupied);
-  hipFree(e->want_dev); hipFree(e->spawned_slots_dev); hipFree(e->spawn_scratch); hipHostFree(e->want_host); hipFree(e->blk_desc); hipFree(e->blk_desc_back); hipFree(e->n_blocks_dev); hipFree(e->n_blocks_back); hipFree(e->band_prefix); hipFree(e->tile_spill); hipFree(e->spawn_rec_dev); hipFree(e->find_dev); hipFree(e->step_flags_dev); hipFree(e->query_scratch); hipFree(e->scan_tile_sums); hipFree(e->write_scratch); hipFree(e->sel_groups_dev); hipFree(e->field_scratch); hipFree(e->pairs_scratch);
+  hipFree(e->want_dev); hipFree(e->spawned_slots_dev); hipFree(e->spawn_scratch); hipHostFree(e->want_host); hipFree(e->blk_desc); hipFree(e->blk_desc_back); hipFree(e->n_blocks_dev); hipFree(e->n_blocks_back); hipFree(e->band_prefix); hipFree(e->tile_spill); hipFree(e->spawn_rec_dev); hipFree(e->find_dev); hipFree(e->step_flags_dev); hipFree(e->query_scratch); hipFree(e->scan_tile_sums); hipFree(e->write_scratch); hipFree(e->sel_groups_dev); hipFree(e->field_scratch); hipFree(e->flow_scratch); hipFree(e->pairs_scratch);
   for (auto& t : e->timed) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
   for (auto ev : e->event_pool) hipEventDestroy(ev);
   if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
@@ -1312,6 +1313,7 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
 #include "cs_select.hip.inc"
 #include "cs_field.hip.inc"
 #include "cs_hlp_field.hip.inc"
+#include "cs_flow_solve.hip.inc"
 #include "cs_near.hip.inc"
 #include "cs_close_pairs.hip.inc"
 #include "cs_clusters.hip.inc"

@@ -2854,6 +2854,7 @@ struct cs_engine {
     b += sel_groups_cap * sizeof(SelGroupDev);
     b += field_scratch_bytes;  // the raster of the last cs_agent_field (cs_field.hip.inc)
     b += hlp_field_bytes();    // the field planners' samples and their table (cs_hlp_field.hip.inc)
+    b += flow_scratch_bytes;   // the rasters of the last cs_flow_field_solve (cs_flow_solve.hip.inc)
     b += pairs_scratch_bytes;  // the kept part of the lists of the distance queries, at most 16 MiB (cs_near.hip.inc)
     return b;
   }
@@ -2875,6 +2876,9 @@ struct cs_engine {
   // the raster of cs_agent_field (cs_field.hip.inc): grown to the largest raster asked for, never shrunk
   void* field_scratch = nullptr;
   size_t field_scratch_bytes = 0;
+  // the rasters of cs_flow_field_solve (cs_flow_solve.hip.inc): grown to the largest solve asked for, never shrunk
+  void* flow_scratch = nullptr;
+  size_t flow_scratch_bytes = 0;
   // the lists of cs_close_pairs, cs_agent_clusters and cs_agent_neighbours (PairsScratch, cs_near.hip.inc): kept while
   // they need at most PAIRS_SCRATCH_KEEP bytes; a larger list is allocated for its call and freed before it returns
   void* pairs_scratch = nullptr;

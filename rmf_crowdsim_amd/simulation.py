@@ -367,6 +367,7 @@ class FieldPlanner(HighLevelPlanner):
         self.sampling = sampling
         self.vectors = self._checked(vectors, None)
         self._bound = []  # (lib or mesh registrar, engine or mesh, planner handle) of every device registration
+        self._sims = []   # the simulations and meshes it is registered with (solve)
 
     @staticmethod
     def _checked(vectors, shape):
@@ -381,6 +382,20 @@ class FieldPlanner(HighLevelPlanner):
         for lib, engine, handle in self._bound:
             if lib.cs_hlp_field_update(engine, handle, self.vectors.ctypes.data_as(C.POINTER(C.c_float))) != 0:
                 raise CrowdSimError(lib.cs_last_error(engine).decode())
+
+    def _registered_with(self, sim):
+        self._sims.append(sim)
+
+    def solve(self, goals, speed, **how):
+        """Solve the flow field to `goals` on the device and write it into this planner, in every simulation it is
+        registered with (Simulation.solve_flow_field with planner=self, whose keywords `how` are).  Steps already queued
+        use the old values.  -> (vectors | None, dist | None, stats) of the last of them."""
+        if not self._sims:
+            raise CrowdSimError("FieldPlanner.solve: the planner is registered with no simulation yet")
+        out = None
+        for sim in self._sims:
+            out = sim.solve_flow_field(self.origin, self.cell, goals, speed, planner=self, **how)
+        return out
 
     def get_desired_velocity(self, agent, time):
         return field_velocity(self.origin, self.cell, self.vectors, self.sampling == "bilinear", agent.position[0],
@@ -1104,6 +1119,161 @@ def flow_field_to_goals(blocked, goals, origin, cell, speed, return_distance=Fal
     return (out, dist) if return_distance else out
 
 
+FLOW_STEPS = tuple((dx, dy) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if dx or dy)  # the order of cs_flow_field_solve
+
+
+def _flow_masks(goals, blocked, slowness, counts):
+    goals = np.asarray(goals)
+    if goals.ndim != 2 or goals.size == 0:
+        raise CrowdSimError("flow field: goals is an array of shape (ny, nx)")
+    shape = goals.shape
+    goals = np.ascontiguousarray(goals != 0, dtype=np.uint8)
+    if blocked is not None:
+        blocked = np.asarray(blocked)
+        if blocked.shape != shape:
+            raise CrowdSimError("flow field: blocked has the shape of goals")
+        blocked = np.ascontiguousarray(blocked != 0, dtype=np.uint8)
+    if slowness is not None:
+        slowness = np.ascontiguousarray(np.asarray(slowness, dtype=np.float32))
+        if slowness.shape != shape:
+            raise CrowdSimError("flow field: slowness has the shape of goals")
+    if counts is not None:
+        counts = np.ascontiguousarray(np.asarray(counts, dtype=np.uint32))
+        if counts.shape != shape:
+            raise CrowdSimError("flow field: counts has the shape of goals")
+    return goals, blocked, slowness, counts
+
+
+def flow_field_solve_host(blocked, goals, cell, speed, *, slowness=None, counts=None, density_weight=0.0):
+    """The rule of cs_flow_field_solve (include/crowdstep_state.h, "Solving a flow field on the device") on the host, as a
+    heap Dijkstra in f64 with exactly the rule's operations, each rounded once: what the device solver is checked against
+    bit for bit, and what a library without the call falls back to.  blocked (or None), goals: (ny, nx), non-zero = set;
+    cell: a scalar or (w, h); slowness: float32 (ny, nx) or None; counts: uint32 (ny, nx), what agent_field reports, used
+    when density_weight != 0.  A step from a bin costs len(step) * s(bin), s = slowness * (1 + density_weight * count).
+    -> (vectors float32 (ny, nx, 2), dist float64 (ny, nx)): zero at goals, NaN / inf at blocked and unreachable bins."""
+    import heapq
+    import math
+    goals, blocked, slowness, counts = _flow_masks(goals, blocked, slowness, counts)
+    cell = np.asarray(cell, dtype=np.float64).reshape(-1)
+    cw, ch = float(cell[0]), float(cell[-1])
+    speed, w = float(speed), float(density_weight)
+    if not (math.isfinite(speed) and speed >= 0.0 and math.isfinite(w) and 0.0 <= w <= 2.0 ** 32):
+        raise CrowdSimError("flow field: speed is finite and >= 0, density_weight in [0, 2^32]")
+    if slowness is not None and not (np.isfinite(slowness).all() and (slowness >= 0).all()):
+        raise CrowdSimError("flow field: a slowness that is NaN, infinite or negative")
+    if w != 0.0 and counts is None:
+        raise CrowdSimError("flow field: a density_weight needs counts")
+    ny, nx = goals.shape
+    wall = blocked.astype(bool).tolist() if blocked is not None else [[False] * nx for _ in range(ny)]
+    diag = math.sqrt(cw * cw + ch * ch)
+    lens = [diag if dx and dy else cw if dx else ch for dx, dy in FLOW_STEPS]
+    slow = [[1.0] * nx for _ in range(ny)] if slowness is None else slowness.astype(np.float64).tolist()
+    if w != 0.0:
+        cnt = counts.tolist()
+        slow = [[slow[iy][ix] * (1.0 + w * float(cnt[iy][ix])) for ix in range(nx)] for iy in range(ny)]
+    inf = math.inf
+    dist = [[inf] * nx for _ in range(ny)]
+    heap = []
+    for iy, ix in zip(*np.nonzero(goals)):
+        if not wall[iy][ix]:
+            dist[iy][ix] = 0.0
+            heap.append((0.0, int(iy), int(ix)))
+    heapq.heapify(heap)
+    while heap:
+        d, iy, ix = heapq.heappop(heap)
+        if d > dist[iy][ix]:
+            continue
+        # every bin (jx, jy) whose step k leads here: (jx + dx, jy + dy) == (ix, iy)
+        for k, (dx, dy) in enumerate(FLOW_STEPS):
+            jx, jy = ix - dx, iy - dy
+            if not (0 <= jx < nx and 0 <= jy < ny) or wall[jy][jx]:
+                continue
+            if dx and dy and (wall[jy][ix] or wall[iy][jx]):
+                continue
+            c = d + lens[k] * slow[jy][jx]
+            if c < dist[jy][jx]:
+                dist[jy][jx] = c
+                heapq.heappush(heap, (c, jy, jx))
+    table = []
+    with np.errstate(all="ignore"):
+        for k, (dx, dy) in enumerate(FLOW_STEPS):
+            sx, sy, n = np.float64(dx * cw), np.float64(dy * ch), np.float64(lens[k])
+            table.append((np.float32((np.float64(speed) * sx) / n), np.float32((np.float64(speed) * sy) / n)))
+    vectors = np.full((ny, nx, 2), np.nan, dtype=np.float32)
+    for iy in range(ny):
+        for ix in range(nx):
+            if wall[iy][ix] or dist[iy][ix] == inf:
+                continue
+            if goals[iy, ix]:
+                vectors[iy, ix] = (0.0, 0.0)
+                continue
+            best, pick = inf, None
+            for k, (dx, dy) in enumerate(FLOW_STEPS):
+                jx, jy = ix + dx, iy + dy
+                if not (0 <= jx < nx and 0 <= jy < ny) or wall[jy][jx]:
+                    continue
+                if dx and dy and (wall[iy][jx] or wall[jy][ix]):
+                    continue
+                c = dist[jy][jx] + lens[k] * slow[iy][ix]
+                if c < best:
+                    best, pick = c, k
+            if pick is not None:
+                vectors[iy, ix] = table[pick]
+    return vectors, np.array(dist, dtype=np.float64).reshape(ny, nx)
+
+
+def flow_solve_call(fn, handle, origin, cell, goals, speed, blocked, slowness, density_weight, sel, hlp, vectors, distance):
+    """cs_flow_field_solve / cs_mesh_flow_field_solve -> (rc, vectors or None, dist or None, {"reached", "rounds"})"""
+    goals, blocked, slowness, _ = _flow_masks(goals, blocked, slowness, None)
+    ny, nx = goals.shape
+    desc = _abi.FlowDesc()
+    desc.raster = field_desc(origin, cell, (ny, nx))
+    u8 = C.POINTER(C.c_uint8)
+    desc.goals = goals.ctypes.data_as(u8)
+    desc.blocked = blocked.ctypes.data_as(u8) if blocked is not None else None
+    desc.slowness = slowness.ctypes.data_as(C.POINTER(C.c_float)) if slowness is not None else None
+    desc.speed, desc.density_weight = float(speed), float(density_weight)
+    desc.density_filter = C.pointer(sel) if sel is not None else None
+    vec = np.zeros((ny, nx, 2), dtype=np.float32) if vectors else None
+    dist = np.zeros((ny, nx), dtype=np.float64) if distance else None
+    stats = _abi.FlowStats()
+    rc = fn(handle, C.byref(desc), 0xFFFFFFFF if hlp is None else hlp,
+            vec.ctypes.data_as(C.POINTER(C.c_float)) if vectors else None,
+            dist.ctypes.data_as(C.POINTER(C.c_double)) if distance else None, C.byref(stats))
+    return rc, vec, dist, {"reached": int(stats.reached), "rounds": int(stats.rounds)}
+
+
+def flow_solve_of(sim, fn, handle, handle_of, origin, cell, goals, speed, blocked, slowness, density_weight, density_filter,
+                  planner, vectors, distance):
+    """solve_flow_field of a Simulation or a NativeTileMesh: the device call, or on a library without it (fn is None)
+    agent_field + flow_field_solve_host + FieldPlanner.update"""
+    shape = np.asarray(goals).shape
+    if planner is not None:
+        if not isinstance(planner, FieldPlanner):
+            raise CrowdSimError("solve_flow_field: planner is a FieldPlanner")
+        same = field_desc(planner.origin, planner.cell, planner.vectors.shape[:2])
+        mine = field_desc(origin, cell, shape if len(shape) == 2 else (0, 0))
+        if bytes(same) != bytes(mine):
+            raise CrowdSimError("solve_flow_field: the planner's raster is not the solve's")
+    hlp = None if planner is None else sim._handle(planner)
+    if fn is not None and (planner is None or planner._bound):
+        sel = None if density_filter is None else selection_struct(density_filter, handle_of)
+        rc, vec, dist, stats = flow_solve_call(fn, handle, origin, cell, goals, speed, blocked, slowness, density_weight,
+                                               sel, hlp, vectors, distance)
+        if rc != 0:
+            raise sim._err()
+        if planner is not None and vec is not None:
+            planner.vectors = vec.copy()  # (the host copy follows what the device now samples)
+        return vec, dist, stats
+    counts = sim.agent_field(origin, cell, shape, density_filter) if float(density_weight) != 0.0 else None
+    vec, dist = flow_field_solve_host(blocked, goals, cell, speed, slowness=slowness, counts=counts,
+                                      density_weight=density_weight)
+    if planner is not None:
+        planner.update(vec)
+    stats = {"reached": int(np.isfinite(dist).sum()), "rounds": 0}
+    return (vec if vectors else None), (dist if distance else None), stats
+
+
 def free_spans(offsets, spans, t0, t1):
     """The complement of merge_leg_intervals' spans inside each leg: per leg a list of (start, end) ABSOLUTE times inside
     [t0[k], t1[k]] during which nobody is within the distance, ascending; spans of zero length are left out."""
@@ -1582,6 +1752,21 @@ class Simulation:
         if rc != 0:
             raise self._err()
         return (count, sums) if velocity else count
+
+    def solve_flow_field(self, origin, cell, goals, speed, *, blocked=None, slowness=None, density_weight=0.0,
+                         density_filter=None, planner=None, vectors=True, distance=False):
+        """Solve a flow field on the device (cs_flow_field_solve, include/crowdstep_state.h): the preferred velocities
+        that lead every bin of the raster (`origin`, `cell`, the shape (ny, nx) of `goals`) to its cheapest goal bin
+        round the `blocked` bins, 8-connected, no corner cutting.  A step out of a bin costs its length times the bin's
+        slowness, `slowness` (float32 (ny, nx), default 1) times 1 + density_weight * (the agents in the bin, those
+        `density_filter` selects): a jam in front of one exit sends people to the other.  `planner`: a FieldPlanner of
+        this raster, registered here; the vectors are written into its device samples behind the steps already queued,
+        and with vectors=False and distance=False no raster crosses the bus.  The call waits for the device.
+        -> (vectors float32 (ny, nx, 2) | None, dist float64 (ny, nx) | None, {"reached": bins with a path, "rounds"}).
+        Distances are the same bits as flow_field_solve_host, which a library without the call falls back to."""
+        return flow_solve_of(self, getattr(self._lib, "cs_flow_field_solve", None), self._engine,
+                             lambda p: self._planner_handles.get(id(p)), origin, cell, goals, speed, blocked, slowness,
+                             density_weight, density_filter, planner, vectors, distance)
 
     def close_pairs(self, distance, a=None, b=None, *, limit=None, distances=False):
         """The pairs of agents closer than `distance`, on the device (cs_close_pairs): contacts, overlaps, near misses.

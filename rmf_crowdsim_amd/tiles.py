@@ -738,6 +738,16 @@ class NativeTileMesh:
             raise self._err()
         return (count, sums) if velocity else count
 
+    def solve_flow_field(self, origin, cell, goals, speed, *, blocked=None, slowness=None, density_weight=0.0,
+                         density_filter=None, planner=None, vectors=True, distance=False):
+        """Simulation.solve_flow_field on the mesh (cs_mesh_flow_field_solve): the counts come by the path of agent_field,
+        then every tile solves the same problem and writes its own copy of the planner's samples; the outputs are the
+        first local tile's.  Collective in the distributed form: every rank passes the same arguments."""
+        from .simulation import flow_solve_of
+        return flow_solve_of(self, getattr(self._lib, "cs_mesh_flow_field_solve", None), self._mesh,
+                             lambda p: self._handles.get(id(p)), origin, cell, goals, speed, blocked, slowness,
+                             density_weight, density_filter, planner, vectors, distance)
+
     def close_pairs(self, distance, a=None, b=None, *, limit=None, distances=False):
         """Simulation.close_pairs on the mesh (cs_mesh_close_pairs): the single engine's answer, byte for byte.  On a mesh
         of more than one tile `distance` is at most halo_cells * cell_size.  Every tile lists the pairs among its own
