@@ -13,6 +13,7 @@
 //                             (location_hash_2d.rs:240-258, zanlungo.rs:49-217, lib.rs:259-359)
 //   cs_kernels_ids.hip.inc    CS_CFG_WIDE_IDS: external ids, the renumbering of device ids (radix sort)
 //   cs_kernels_aux.hip.inc    k_halo_pack/unpack (tiles), k_spawn (lib.rs:199-254), radius query
+//   cs_device_mem.hip.inc     who owns device and pinned memory: the only place that allocates and frees it
 //   cs_engine.hip.inc         the host engine: step state machine, tables, tiles, events
 //   cs_rccl.hip.inc           RCCL bound at first use (halo transport of a tile)
 //   cs_mesh.hip.inc           a crowd cut into tiles behind one handle (cs_mesh_*)
@@ -48,7 +49,6 @@
 #include <cstdint>
 #include <cstdio>
 #include <array>
-#include <cmath>
 #include <cstring>
 #include <functional>
 #include <map>
@@ -72,6 +72,7 @@
 #include "cs_kernels_ids.hip.inc"
 #include "cs_kernels_step.hip.inc"
 #include "cs_kernels_aux.hip.inc"
+#include "cs_device_mem.hip.inc"
 #include "cs_engine.hip.inc"
 #include "cs_rccl.hip.inc"
 
@@ -83,6 +84,16 @@
       return 90;                                                                              \
     }                                                                                         \
   } while (0)
+
+// A kept scratch of a between-step call, grown to `need` bytes (never shrunk).  `oom`: the call's own text for a failed
+// allocation; a failed wait for the stream (the scratch is then still held) reads as HIP_OK_E would have put it.
+static int scratch_reserve(cs_engine* e, DevBytes& scratch, size_t need, const char* oom) {
+  const hipError_t err = scratch.reserve(e->stream, need);
+  if (err == hipSuccess) return 0;
+  if (scratch.get()) e->error = std::string("HIP error: ") + hipGetErrorString(err) + " at hipStreamSynchronize(e->stream)";
+  else e->error = oom;
+  return 90;
+}
 
 // ===========================================================================
 // C ABI (include/crowdstep.h)
@@ -97,32 +108,27 @@ void cs_destroy(cs_engine* e) {
   if (e->stream) hipStreamSynchronize(e->stream);
   if (e->aux_stream) hipStreamSynchronize(e->aux_stream);  // (an exchange made ahead may still be in flight there)
   if (e->rccl_comm && e->rccl_comm_owned && rccl_api::api().comm_destroy) rccl_api::api().comm_destroy(e->rccl_comm);
-  e->free_arrays(e->buf[0]);
-  e->free_arrays(e->buf[1]);
-  hipFree(e->pref); hipFree(e->cell_count); hipFree(e->cell_start); hipFree(e->block_totals);
-  hipFree(e->ext_tab_dev[0]); hipFree(e->ext_tab_dev[1]); hipFree(e->ids_scratch);
-  hipFree(e->ctr); hipHostFree(e->ctr_host); hipFree(e->epi_dev); delete[] e->epi_host; hipFree(e->destroyed); hipFree(e->wp_events);
+  delete[] e->epi_host;
   for (auto& sn : e->snap) {
     if (sn.in_flight) hipEventSynchronize(sn.copied);
-    hipFree(sn.dev); hipHostFree(sn.host); hipFree(sn.count_dev); hipHostFree(sn.count_host);
     if (sn.gathered) hipEventDestroy(sn.gathered);
     if (sn.copied) hipEventDestroy(sn.copied);
   }
   if (e->copy_stream) hipStreamDestroy(e->copy_stream);
-  if (e->peek_host) hipHostFree(e->peek_host);
   if (e->aux_stream) {
     hipStreamSynchronize(e->aux_stream);
     hipStreamDestroy(e->aux_stream);
     hipEventDestroy(e->ev_sorted); hipEventDestroy(e->ev_border); hipEventDestroy(e->ev_xchg);
   }
-  hipFree(e->route_desc_dev); hipFree(e->route_xy_dev); hipFree(e->route_book_dev); hipFree(e->hlp_scale_dev); hipFree(e->route_pending_dev);
-  e->free_hlp_fields();
-  hipFree(e->groups_dev); hipFree(e->sinks_dev); hipFree(e->waypoints_dev);
-  hipFree(e->src_cell_start); hipFree(e->src_sorted); hipFree(e->src_occupied);
-  hipFree(e->want_dev); hipFree(e->spawned_slots_dev); hipFree(e->spawn_scratch); hipHostFree(e->want_host); hipFree(e->blk_desc); hipFree(e->blk_desc_back); hipFree(e->n_blocks_dev); hipFree(e->n_blocks_back); hipFree(e->band_prefix); hipFree(e->tile_spill); hipFree(e->spawn_rec_dev); hipFree(e->find_dev); hipFree(e->step_flags_dev); hipFree(e->query_scratch); hipFree(e->scan_tile_sums); hipFree(e->write_scratch); hipFree(e->sel_groups_dev); hipFree(e->field_scratch); hipFree(e->flow_scratch); hipFree(e->pairs_scratch);
+  e->hlp_field_time_read();
+  for (auto& kv : e->hlp_fields) {
+    if (kv.second.stage_busy) hipEventSynchronize(kv.second.staged);
+    if (kv.second.staged) hipEventDestroy(kv.second.staged);
+  }
   for (auto& t : e->timed) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
   for (auto ev : e->event_pool) hipEventDestroy(ev);
   if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
+  // the engine's members free its device and pinned memory: its device is current, nothing is in flight on its streams
   delete e;
 }
 
@@ -235,9 +241,9 @@ cs_engine* cs_create(const cs_grid_desc* grid, const cs_device_cfg* cfg) {
                       is_tile ? cfg->tile_cy1 : 0, is_tile ? cfg->halo_cells : 0) != 0)
     return create_failed(e, e->error);
   bool ok = true;
-  ok = ok && hipMalloc(&e->ctr, sizeof(Counters)) == hipSuccess;
-  ok = ok && hipHostMalloc(&e->ctr_host, sizeof(Counters)) == hipSuccess;
-  if (ok) hipMemset(e->ctr, 0, sizeof(Counters));
+  ok = ok && e->ctr.alloc(1) == hipSuccess;
+  ok = ok && e->ctr_host.alloc(1) == hipSuccess;
+  if (ok) hipMemset(e->ctr.get(), 0, sizeof(Counters));
   if (const char* v = getenv("CS_FIRST_AGENT_ID")) {  // test knob: ids near the 31-bit limit without 2^31 agents
     e->next_id = std::min<uint64_t>((uint64_t)strtoull(v, nullptr, 10), CS_ID_LIMIT);
     if (e->wide_ids) {  // the EXTERNAL counter, any u64; the device counter starts at 0 with its parity
@@ -249,7 +255,7 @@ cs_engine* cs_create(const cs_grid_desc* grid, const cs_device_cfg* cfg) {
       }
     }
     const uint32_t nid = (uint32_t)e->next_id;
-    if (ok) hipMemcpy(&e->ctr->next_id, &nid, sizeof nid, hipMemcpyHostToDevice);
+    if (ok) hipMemcpy(&e->ctr.get()->next_id, &nid, sizeof nid, hipMemcpyHostToDevice);
   }
   if (!ok || e->upload_sinks() != 0 ||
       e->reserve(cfg && cfg->capacity_hint ? cfg->capacity_hint : 1024) != 0) {
@@ -343,15 +349,15 @@ int cs_remove_agent(cs_engine* e, uint64_t id) {
   uint32_t found[2] = {0xFFFFFFFFu, 0u};
   uint64_t dev = 0;  // (CS_CFG_WIDE_IDS: the external id's device id; otherwise the id itself)
   if (e->dev_id(id, &dev) && dev < 0xFFFFFFFFull && e->n_slots) {
-    if (!e->find_dev && hipMalloc(&e->find_dev, 2 * sizeof(uint32_t)) != hipSuccess) {
+    if (!e->find_dev.get() && e->find_dev.alloc(2) != hipSuccess) {
       e->error = "HIP error while removing an agent";
       return 90;
     }
-    bool ok = hipMemcpyAsync(e->find_dev, found, sizeof found, hipMemcpyHostToDevice, e->stream) == hipSuccess;
+    bool ok = hipMemcpyAsync(e->find_dev.get(), found, sizeof found, hipMemcpyHostToDevice, e->stream) == hipSuccess;
     hipLaunchKernelGGL(k_remove_by_id, dim3((e->n_slots + 255u) / 256u), dim3(256), 0, e->stream, e->gdev, e->buf[e->cur],
-                       e->n_slots, e->ctr, e->gdev.tile, (e->tile && e->ghosts_present) ? 1u : 0u, (uint32_t)dev,
-                       e->find_dev);
-    ok = ok && hipMemcpyAsync(found, e->find_dev, sizeof found, hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
+                       e->n_slots, e->ctr.get(), e->gdev.tile, (e->tile && e->ghosts_present) ? 1u : 0u, (uint32_t)dev,
+                       e->find_dev.get());
+    ok = ok && hipMemcpyAsync(found, e->find_dev.get(), sizeof found, hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
          hipStreamSynchronize(e->stream) == hipSuccess;
     if (!ok) {
       e->error = "HIP error while removing an agent";
@@ -489,12 +495,12 @@ size_t cs_agent_count(cs_engine* e) {
     // walked across a cut and brought ghosts: the agents of this tile are the live records in its owned cells, the ones
     // cs_read_agents lists and the selections count.
     uint32_t owned = 0;
-    bool ok = e->find_dev || hipMalloc(&e->find_dev, 2 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMemsetAsync(e->find_dev, 0, sizeof(uint32_t), e->stream) == hipSuccess;
+    bool ok = e->find_dev.get() || e->find_dev.alloc(2) == hipSuccess;
+    ok = ok && hipMemsetAsync(e->find_dev.get(), 0, sizeof(uint32_t), e->stream) == hipSuccess;
     if (ok)
       hipLaunchKernelGGL(k_tile_count_owned, dim3((e->n_slots + 255u) / 256u), dim3(256), 0, e->stream, e->gdev,
-                         e->buf[e->cur], e->n_slots, e->ctr, e->find_dev);
-    ok = ok && hipMemcpyAsync(&owned, e->find_dev, sizeof owned, hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
+                         e->buf[e->cur], e->n_slots, e->ctr.get(), e->find_dev.get());
+    ok = ok && hipMemcpyAsync(&owned, e->find_dev.get(), sizeof owned, hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
          hipStreamSynchronize(e->stream) == hipSuccess;
     if (ok) return (size_t)owned + e->limbo.size();
     // (the call has no way to fail: cs_last_error says that what follows is the count of the last step)
@@ -605,16 +611,15 @@ static size_t radius_query(cs_engine* e, double radius, double x, double y, std:
   float qox = (float)((x - e->grid.offset_x) - (double)qx * e->grid.cell_size);
   float qoy = (float)((y - e->grid.offset_y) - (double)qy * e->grid.cell_size);
   uint32_t qcap = (uint32_t)std::max<size_t>(1, std::min<size_t>(cap, 1u << 22));
-  uint32_t* d_out = nullptr;
-  float* d_d2 = nullptr;
-  uint32_t* d_cnt = nullptr;
-  bool ok = hipMalloc(&d_out, qcap * sizeof(uint32_t)) == hipSuccess &&
-            hipMalloc(&d_d2, qcap * sizeof(float)) == hipSuccess &&
-            hipMalloc(&d_cnt, sizeof(uint32_t)) == hipSuccess;
+  DevBuf<uint32_t> out_mem, cnt_mem;
+  DevBuf<float> d2_mem;
+  bool ok = out_mem.alloc(qcap) == hipSuccess && d2_mem.alloc(qcap) == hipSuccess && cnt_mem.alloc(1) == hipSuccess;
+  uint32_t *d_out = out_mem.get(), *d_cnt = cnt_mem.get();
+  float* d_d2 = d2_mem.get();
   uint32_t cnt = 0;
   if (ok) {
     hipLaunchKernelGGL(k_query_radius, dim3(1), dim3(64), 0, e->stream, e->gdev, e->buf[e->cur],
-                       e->cell_start, lx, hx, ly, hy, (uint32_t)qx, (uint32_t)qy, qox, qoy, (float)radius,
+                       e->cell_start.get(), lx, hx, ly, hy, (uint32_t)qx, (uint32_t)qy, qox, qoy, (float)radius,
                        d_out, d_d2, qcap, d_cnt);
     ok = hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
          hipStreamSynchronize(e->stream) == hipSuccess;
@@ -626,9 +631,6 @@ static size_t radius_query(cs_engine* e, double radius, double x, double y, std:
       ok = ok && hipMemcpy(d2->data(), d_d2, m * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
     }
   }
-  hipFree(d_out);
-  hipFree(d_d2);
-  hipFree(d_cnt);
   if (!ok) {
     e->error = "HIP error in a spatial query";
     ids->clear();
@@ -692,17 +694,9 @@ static int radius_query_batch(cs_engine* e, size_t n, const double* xy, const do
   const size_t o_ids = up(n * sizeof(QueryDev)), o_d2 = o_ids + up(n * cap * sizeof(uint32_t)),
                o_cells = o_d2 + up(n * cap * sizeof(float)), o_cnt = o_cells + up(n * cap * sizeof(uint32_t)),
                total = o_cnt + up(n * sizeof(uint32_t));
-  bool ok = true;
-  if (total > e->query_scratch_bytes) {
-    hipStreamSynchronize(e->stream);
-    hipFree(e->query_scratch);
-    e->query_scratch = nullptr;
-    e->query_scratch_bytes = 0;
-    ok = hipMalloc(&e->query_scratch, total + total / 4) == hipSuccess;
-    if (ok) e->query_scratch_bytes = total + total / 4;
-  }
+  bool ok = e->query_scratch.reserve(e->stream, total, Grow::quarter) == hipSuccess;
   if (ok) {
-    unsigned char* base = static_cast<unsigned char*>(e->query_scratch);
+    unsigned char* base = static_cast<unsigned char*>(e->query_scratch.get());
     QueryDev* d_q = reinterpret_cast<QueryDev*>(base);
     uint32_t* d_ids = reinterpret_cast<uint32_t*>(base + o_ids);
     float* d_d2 = reinterpret_cast<float*>(base + o_d2);
@@ -710,7 +704,7 @@ static int radius_query_batch(cs_engine* e, size_t n, const double* xy, const do
     uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + o_cnt);
     ok = hipMemcpyAsync(d_q, q.data(), n * sizeof(QueryDev), hipMemcpyHostToDevice, e->stream) == hipSuccess;
     hipLaunchKernelGGL(k_query_radius_batch, dim3((uint32_t)n), dim3(64), 0, e->stream, e->gdev, e->buf[e->cur],
-                       e->cell_start, d_q, (uint32_t)n, (uint32_t)e->gnx, (e->tile && e->ghosts_present && !with_ghosts) ? 1u : 0u, d_ids,
+                       e->cell_start.get(), d_q, (uint32_t)n, (uint32_t)e->gnx, (e->tile && e->ghosts_present && !with_ghosts) ? 1u : 0u, d_ids,
                        d_d2, d_cells, (uint32_t)cap, d_cnt);
     ok = ok && hipMemcpyAsync(counts->data(), d_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
          hipMemcpyAsync(ids->data(), d_ids, n * cap * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
@@ -752,12 +746,12 @@ int cs_query_radius_batch(cs_engine* e, size_t n, const double* xy, const double
 // ascending id, (5) the answers go back by slot and the step kernels read them instead of evaluating a planner.
 static int lp_callbacks_eval(cs_engine* e, const StepParams& P, const EpilogueCtx* Ep) {
   const uint32_t n = e->n_slots;
-  hipLaunchKernelGGL(k_lp_recommended, dim3((n + 255u) / 256u), dim3(256), 0, e->stream, P, e->view(e->cur), Ep, e->pref,
-                     e->lp_vel);
+  hipLaunchKernelGGL(k_lp_recommended, dim3((n + 255u) / 256u), dim3(256), 0, e->stream, P, e->view(e->cur), Ep, e->pref.get(),
+                     e->lp_vel.get());
   cs_engine::HostState h;
   if (int rc = e->download(&h)) return rc;  // (synchronises the stream)
   std::vector<float2> rec(n);
-  if (hipMemcpy(rec.data(), e->lp_vel, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost) != hipSuccess) {
+  if (hipMemcpy(rec.data(), e->lp_vel.get(), (size_t)n * sizeof(float2), hipMemcpyDeviceToHost) != hipSuccess) {
     e->error = "HIP error in a host local planner's turn";
     return 90;
   }
@@ -843,7 +837,7 @@ static int lp_callbacks_eval(cs_engine* e, const StepParams& P, const EpilogueCt
     }
     for (size_t k = 0; k < m; ++k) out[slots[k]] = make_float2((float)answer[2 * k], (float)answer[2 * k + 1]);
   }
-  if (hipMemcpyAsync(e->lp_vel, out.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
+  if (hipMemcpyAsync(e->lp_vel.get(), out.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
       hipStreamSynchronize(e->stream) != hipSuccess) {  // (`out` leaves scope)
     e->error = "HIP error in a host local planner's turn";
     return 90;
@@ -1256,10 +1250,10 @@ int cs_tile_step_rccl(cs_engine* e, double dt_seconds, cs_step_report* report) {
     }
     const size_t ns = e->sinks.size();
     if (int rc = e->reserve_step_flags(ns)) return rc;
-    if (int rc = e->spawn_probe_dev(dt_seconds, e->step_flags_dev)) return rc;
-    if (int rc = cs_allreduce_max_i32_rccl(e, e->step_flags_dev, ns)) return rc;
+    if (int rc = e->spawn_probe_dev(dt_seconds, e->step_flags_dev.get())) return rc;
+    if (int rc = cs_allreduce_max_i32_rccl(e, e->step_flags_dev.get(), ns)) return rc;
     e->step_colls |= 2u;
-    if (int rc = e->spawn_commit_dev(e->step_flags_dev)) return rc;
+    if (int rc = e->spawn_commit_dev(e->step_flags_dev.get())) return rc;
   }
   // CS_CFG_TILE_OVERLAP: the step puts the border windows' launch on the second stream; the next
   // step's exchange follows them there while the interior windows still run on the engine's stream
@@ -1271,7 +1265,7 @@ int cs_tile_step_rccl(cs_engine* e, double dt_seconds, cs_step_report* report) {
     e->border_on_aux = false;
     if (e->early_pending) {  // (the border windows are the first workgroups of the ONE launch: wait for the last of them)
       e->early_pending = false;
-      hipLaunchKernelGGL(k_wait_border, dim3(1), dim3(64), 0, e->aux_stream, e->ctr, e->early_seq);
+      hipLaunchKernelGGL(k_wait_border, dim3(1), dim3(64), 0, e->aux_stream, e->ctr.get(), e->early_seq);
     }
     if (int rc2 = halo_exchange_rccl_on(e, -1, e->aux_stream)) return rc2;
     HIP_OK_E(e, hipEventRecord(e->ev_xchg, e->aux_stream));
@@ -1299,7 +1293,7 @@ static int tile_zombie_collectives(cs_engine* e, uint32_t done) {
   if (!(done & 2u) && !e->sinks.empty()) {
     const size_t ns = e->sinks.size();
     if (int rc = e->reserve_step_flags(ns)) return rc;
-    if (int rc = cs_allreduce_max_i32_rccl(e, e->step_flags_dev, ns)) return rc;
+    if (int rc = cs_allreduce_max_i32_rccl(e, e->step_flags_dev.get(), ns)) return rc;
   }
   return 0;
 }

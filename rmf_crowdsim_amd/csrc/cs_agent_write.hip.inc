@@ -230,22 +230,10 @@ int write_prepare(cs_engine* e, const cs_agent_view* in, size_t n, uint32_t fiel
 // the engine's scratch for calls that address agents by id (the write, and the batched read and remove of
 // cs_agents_by_id.hip.inc): grown as needed, never shrunk
 int write_scratch_reserve(cs_engine* e, size_t need) {
-  if (need > e->write_scratch_bytes) {
-    if (e->write_scratch) {
-      if (hipStreamSynchronize(e->stream) != hipSuccess) {
-        e->error = "HIP error while writing agents";
-        return 90;
-      }
-      hipFree(e->write_scratch);
-    }
-    const size_t grow = std::max(need, e->write_scratch_bytes + e->write_scratch_bytes / 2);
-    e->write_scratch = nullptr;
-    e->write_scratch_bytes = 0;
-    if (hipMalloc(&e->write_scratch, grow) != hipSuccess) {
-      e->error = "HIP error while writing agents (scratch allocation)";
-      return 90;
-    }
-    e->write_scratch_bytes = grow;
+  if (e->write_scratch.reserve(e->stream, need, Grow::half) != hipSuccess) {
+    // (still holding the old scratch: the wait for the stream failed, not the allocation)
+    e->error = e->write_scratch.get() ? "HIP error while writing agents" : "HIP error while writing agents (scratch allocation)";
+    return 90;
   }
   return 0;
 }
@@ -258,7 +246,7 @@ int write_scratch(cs_engine* e, WritePlan* p) {
   const size_t b_mov = p->any_mover ? up(n * sizeof(HaloRecord)) : 0u;
   const size_t need = b_keys + b_recs + b_slot + b_words + b_nmov + b_mov;
   if (int rc = write_scratch_reserve(e, need)) return rc;
-  unsigned char* s = static_cast<unsigned char*>(e->write_scratch);
+  unsigned char* s = static_cast<unsigned char*>(e->write_scratch.get());
   p->d_keys = reinterpret_cast<uint32_t*>(s);
   p->d_recs = reinterpret_cast<WriteRec*>(s + b_keys);
   p->d_slot = reinterpret_cast<uint32_t*>(s + b_keys + b_recs);
@@ -288,11 +276,11 @@ void write_launch_match(cs_engine* e, const uint32_t* d_keys, size_t n, uint32_t
     const uint32_t blocks = (uint32_t)std::max<uint64_t>(
         1, std::min<uint64_t>((e->n_slots + WRITE_STAGED_BLOCK - 1u) / WRITE_STAGED_BLOCK, (uint64_t)n_cu * per_cu));
     hipLaunchKernelGGL(k_write_match<true>, dim3(blocks), dim3(WRITE_STAGED_BLOCK), lds, e->stream, e->gdev, e->buf[e->cur],
-                       e->n_slots, e->ctr, e->tile ? 1u : 0u, owned_only, d_keys, (uint32_t)n, d_slot, meta_dev,
+                       e->n_slots, e->ctr.get(), e->tile ? 1u : 0u, owned_only, d_keys, (uint32_t)n, d_slot, meta_dev,
                        d_count);
   } else {
     hipLaunchKernelGGL(k_write_match<false>, dim3((e->n_slots + WRITE_MATCH_BLOCK - 1u) / WRITE_MATCH_BLOCK),
-                       dim3(WRITE_MATCH_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots, e->ctr,
+                       dim3(WRITE_MATCH_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots, e->ctr.get(),
                        e->tile ? 1u : 0u, owned_only, d_keys, (uint32_t)n, d_slot, meta_dev, d_count);
   }
 }

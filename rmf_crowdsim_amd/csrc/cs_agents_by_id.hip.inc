@@ -108,7 +108,7 @@ int ids_match(cs_engine* e, IdBatch* b, bool want_meta, bool records, size_t ext
   const size_t b_keys = up(n * sizeof(uint32_t)), b_slot = b_keys, b_words = up((n + 1) * sizeof(uint32_t));
   const size_t b_recs = records ? up(n * sizeof(AgentRec)) : 0u;
   if (int rc = write_scratch_reserve(e, b_keys + b_slot + b_words + b_recs + extra_bytes)) return rc;
-  unsigned char* s = static_cast<unsigned char*>(e->write_scratch);
+  unsigned char* s = static_cast<unsigned char*>(e->write_scratch.get());
   if (extra) *extra = s + b_keys + b_slot + b_words + b_recs;
   b->d_keys = reinterpret_cast<uint32_t*>(s);
   b->d_slot = reinterpret_cast<uint32_t*>(s + b_keys);

@@ -231,8 +231,8 @@ int pairs_run(cs_engine* e, const PairsArgs& P, size_t want, bool want_d2, std::
   unsigned long long* hdr = nullptr;
   if (int rc = pairs_header(e, &hdr)) return rc;
   const uint32_t blocks = (n + PAIRS_BLOCK - 1u) / PAIRS_BLOCK;
-  hipLaunchKernelGGL(k_pairs_count, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n, e->cell_start,
-                     e->sel_groups_dev, P, hdr);
+  hipLaunchKernelGGL(k_pairs_count, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n, e->cell_start.get(),
+                     e->sel_groups_dev.get(), P, hdr);
   HIP_OK_E(e, hipGetLastError());
   unsigned long long found = 0;
   if (int rc = pairs_read_count(e, hdr, &found)) return rc;
@@ -245,8 +245,8 @@ int pairs_run(cs_engine* e, const PairsArgs& P, size_t want, bool want_d2, std::
   PairsScratch sc(e);
   PairsArrays A;
   if (int rc = pairs_arrays(&sc, found, want_d2, false, &A)) return rc;
-  hipLaunchKernelGGL(k_pairs_emit, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n, e->cell_start,
-                     e->sel_groups_dev, P, hdr, A.keys, A.d2, (unsigned long long)found);
+  hipLaunchKernelGGL(k_pairs_emit, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n, e->cell_start.get(),
+                     e->sel_groups_dev.get(), P, hdr, A.keys, A.d2, (unsigned long long)found);
   HIP_OK_E(e, hipGetLastError());
   return pairs_list_end(e, hdr, A, found, want, out);
 }
@@ -312,7 +312,7 @@ int pairs_cross(cs_engine* e, const std::vector<PairsBandRec>& local, const std:
   // the records stay where they are: where they lie in the kept scratch, the list takes an allocation of its own
   PairsScratch sc(e);
   PairsArrays A;
-  if (int rc = pairs_arrays(&sc, found, want_d2, recs.temp == nullptr, &A)) return rc;
+  if (int rc = pairs_arrays(&sc, found, want_d2, recs.temp.get() == nullptr, &A)) return rc;
   hipLaunchKernelGGL(k_pairs_cross_emit, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, d_l, n_l, d_f, n_f, dist2, hdr, A.keys,
                      A.d2, (unsigned long long)found);
   HIP_OK_E(e, hipGetLastError());

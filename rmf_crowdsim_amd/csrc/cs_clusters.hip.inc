@@ -419,12 +419,10 @@ struct ClustersArena {
   PairsScratch sc;
   unsigned char* base = nullptr;
   size_t used = 0, room = 0;
-  std::vector<void*> extra;
+  std::vector<DevBytes> extra;
   explicit ClustersArena(cs_engine* e) : sc(e) {}
   ~ClustersArena() {
-    if (extra.empty()) return;
-    hipStreamSynchronize(sc.e->stream);
-    for (void* p : extra) hipFree(p);
+    if (!extra.empty()) hipStreamSynchronize(sc.e->stream);  // (then `extra` frees them)
   }
   // `first` bytes now; `wish`: what the call may need in all (asked for at once while that keeps it in the kept scratch)
   int open(size_t first, size_t wish) {
@@ -438,13 +436,13 @@ struct ClustersArena {
   // room for `bytes` more in ONE block
   int reserve(size_t bytes) {
     if (used + bytes <= room) return 0;
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) {
+    DevBytes q;
+    if (q.alloc(bytes) != hipSuccess) {
       sc.e->error = "agent_clusters: out of device memory";
       return 90;
     }
-    extra.push_back(q);
-    base = static_cast<unsigned char*>(q);
+    base = static_cast<unsigned char*>(q.get());
+    extra.push_back(std::move(q));
     used = 0;
     room = bytes;
     return 0;
@@ -477,16 +475,11 @@ struct ClustersOut {
 // mesh: the sorted member keys of a tile stay on its device until the label map is applied
 struct ClustersHold {
   cs_engine* e = nullptr;
-  void* mem = nullptr;
+  DevBytes mem;
   unsigned long long* keys = nullptr;
   uint32_t n = 0;
-  ClustersHold() = default;
-  ClustersHold(const ClustersHold&) = delete;
-  ClustersHold& operator=(const ClustersHold&) = delete;
   ~ClustersHold() {
-    if (!mem) return;
-    hipStreamSynchronize(e->stream);
-    hipFree(mem);
+    if (mem.get()) hipStreamSynchronize(e->stream);  // (then `mem` frees it)
   }
 };
 
@@ -525,10 +518,10 @@ int clusters_run(cs_engine* e, const PairsArgs& P, uint64_t min_size, size_t wan
   HIP_OK_E(e, hipMemsetAsync(hdr, 0, 256u, e->stream));
   HIP_OK_E(e, hipMemsetAsync(min_id, 0xFF, (size_t)n * sizeof(uint32_t), e->stream));
   HIP_OK_E(e, hipMemsetAsync(size, 0, (size_t)n * sizeof(uint32_t), e->stream));
-  hipLaunchKernelGGL(k_clusters_init, grid, block, 0, e->stream, e->gdev, e->buf[e->cur], n, e->cell_start, e->sel_groups_dev, P,
+  hipLaunchKernelGGL(k_clusters_init, grid, block, 0, e->stream, e->gdev, e->buf[e->cur], n, e->cell_start.get(), e->sel_groups_dev.get(), P,
                      parent);
   if (P.dist2 > 0.0) {  // (distance 0: the comparison is strict, every member is its own cluster)
-    hipLaunchKernelGGL(k_clusters_link, grid, block, 0, e->stream, e->gdev, e->buf[e->cur], n, e->cell_start, P, parent);
+    hipLaunchKernelGGL(k_clusters_link, grid, block, 0, e->stream, e->gdev, e->buf[e->cur], n, e->cell_start.get(), P, parent);
     hipLaunchKernelGGL(k_clusters_flatten, grid, block, 0, e->stream, parent, n);
   }
   hipLaunchKernelGGL(k_clusters_label, grid, block, 0, e->stream, e->buf[e->cur].id, parent, n, min_id, size);
@@ -593,13 +586,12 @@ int clusters_run(cs_engine* e, const PairsArgs& P, uint64_t min_size, size_t wan
   if (list_ids) {
     unsigned char* p = nullptr;
     if (hold) {
-      if (hipMalloc(&hold->mem, need_ids) != hipSuccess) {
-        hold->mem = nullptr;
+      if (hold->mem.alloc(need_ids) != hipSuccess) {
         e->error = "agent_clusters: out of device memory";
         return 90;
       }
       hold->e = e;
-      p = static_cast<unsigned char*>(hold->mem);
+      p = static_cast<unsigned char*>(hold->mem.get());
     } else {
       p = A.take(need_ids);
     }

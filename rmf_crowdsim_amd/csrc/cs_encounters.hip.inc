@@ -378,7 +378,7 @@ int enc_run(cs_engine* e, const PairsArgs& P, const EncArgs& E, size_t want, std
   if (int rc = pairs_header(e, &hdr)) return rc;
   const uint32_t blocks = (n + PAIRS_BLOCK - 1u) / PAIRS_BLOCK;
   hipLaunchKernelGGL(k_encounters_count, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n,
-                     e->cell_start, e->sel_groups_dev, P, E, hdr);
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, E, hdr);
   HIP_OK_E(e, hipGetLastError());
   unsigned long long found = 0;
   if (int rc = pairs_read_count(e, hdr, &found)) return rc;
@@ -392,7 +392,7 @@ int enc_run(cs_engine* e, const PairsArgs& P, const EncArgs& E, size_t want, std
   EncArrays A;
   if (int rc = enc_arrays(&sc, found, false, &A)) return rc;
   hipLaunchKernelGGL(k_encounters_emit, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n,
-                     e->cell_start, e->sel_groups_dev, P, E, hdr, A.keys, A.index, A.t, A.m2, (unsigned long long)found);
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, E, hdr, A.keys, A.index, A.t, A.m2, (unsigned long long)found);
   HIP_OK_E(e, hipGetLastError());
   return enc_list_end(e, hdr, A, found, want, out);
 }
@@ -427,7 +427,7 @@ int enc_band_export(cs_mesh* m, size_t local, const PairsArgs& P, const EncArgs&
   EncBandRec* d_rec = reinterpret_cast<EncBandRec*>(p + 256u);
   HIP_OK_E(e, hipMemsetAsync(d_count, 0, sizeof(uint32_t), e->stream));
   hipLaunchKernelGGL(k_encounters_band, dim3((n + PAIRS_BLOCK - 1u) / PAIRS_BLOCK), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev,
-                     e->buf[e->cur], n, e->cell_start, e->sel_groups_dev, P, edges, m->index_of[local], d_rec, n, d_count);
+                     e->buf[e->cur], n, e->cell_start.get(), e->sel_groups_dev.get(), P, edges, m->index_of[local], d_rec, n, d_count);
   HIP_OK_E(e, hipGetLastError());
   uint32_t found = 0;
   HIP_OK_E(e, hipMemcpyAsync(&found, d_count, sizeof found, hipMemcpyDeviceToHost, e->stream));
@@ -478,7 +478,7 @@ int enc_cross(cs_engine* e, const std::vector<EncBandRec>& local, const std::vec
   // the records stay where they are: where they lie in the kept scratch, the list takes an allocation of its own
   PairsScratch sc(e);
   EncArrays A;
-  if (int rc = enc_arrays(&sc, found, recs.temp == nullptr, &A)) return rc;
+  if (int rc = enc_arrays(&sc, found, recs.temp.get() == nullptr, &A)) return rc;
   hipLaunchKernelGGL(k_encounters_cross_emit, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, d_l, n_l, d_f, n_f, range2, E,
                      hdr, A.keys, A.index, A.t, A.m2, (unsigned long long)found);
   HIP_OK_E(e, hipGetLastError());

@@ -62,8 +62,8 @@ struct HlpFieldDev {
 struct HostHlpField {
   cs_field_desc d;
   uint32_t sampling = 0;
-  float2* data = nullptr;
-  float2* stage = nullptr;
+  DevBuf<float2> data;
+  PinnedBuf<float2> stage;
   hipEvent_t staged = nullptr;
   bool stage_busy = false;
 };
@@ -169,28 +169,27 @@ struct cs_engine {
   std::string poison_error = "Index out of bounds";  // what every later call of a poisoned engine reports
 
   // agent buffers: buf[cur] holds the state, buf[cur^1] is the scatter / step target
-  AgentArrays buf[2] = {};
+  AgentArrays buf[2] = {};  // (views of buf_mem, which owns the columns)
+  AgentBuf buf_mem[2];
   int cur = 0;
   uint64_t cap = 0;
   uint32_t n_slots = 0;     // slots in use in buf[cur]
   bool sorted = true;       // buf[cur] is in cell order, cell_start/n_alive match it
   bool hist_valid = false;  // cell_count + rank describe buf[cur]
   bool occ_valid = false;   // src_occupied describes the current positions
-  float2* pref = nullptr;   // callback-HLP velocities in sorted order
-  uint32_t* cell_count = nullptr;
-  uint32_t* cell_start = nullptr;
-  uint32_t* block_totals = nullptr;
+  DevBuf<float2> pref;      // callback-HLP velocities in sorted order
+  DevBuf<uint32_t> cell_count, cell_start, block_totals;
   uint32_t n_scan_blocks = 0;
-  Counters* ctr = nullptr;       // device
-  Counters* ctr_host = nullptr;  // pinned
-  uint2* destroyed = nullptr;
+  DevBuf<Counters> ctr;
+  PinnedBuf<Counters> ctr_host;
+  DevBuf<uint2> destroyed;
   uint32_t destroyed_cap = 0;
-  WpEvent* wp_events = nullptr;
+  DevBuf<WpEvent> wp_events;
   uint32_t wp_events_cap = 0;
-  BlockDesc* blk_desc = nullptr;  // work decomposition of the tiled neighbour kernel
+  DevBuf<BlockDesc> blk_desc;  // work decomposition of the tiled neighbour kernel
   uint32_t blk_desc_cap = 0;
-  uint32_t* n_blocks_dev = nullptr;
-  EpilogueCtx* epi_dev = nullptr;   // the step kernels' EpilogueCtx, one per output buffer (device)
+  DevBuf<uint32_t> n_blocks_dev;
+  DevBuf<EpilogueCtx> epi_dev;      // the step kernels' EpilogueCtx, one per output buffer (device)
   EpilogueCtx* epi_host = nullptr;  // ... and what was written there last
   bool epi_valid[2] = {false, false};
   double max_eyesight = 0.0;
@@ -204,17 +203,16 @@ struct cs_engine {
   uint32_t tile_target = TILE_THREADS;  // most agents a band window may hold (greedy windows)
   uint32_t tile_stage_cap = 0;  // test knob: the staging bound the window builder works with (0 = the real one)
   uint32_t tile_windows_cap = 0;  // test knob: the launch is sized for at most this many band windows (0 = the bound)
-  uint32_t* band_prefix = nullptr;
-  uint32_t* tile_spill = nullptr;  // spilled neighbour-list rows of the tiled kernel, per workgroup
-  uint64_t tile_spill_words = 0;
+  DevBuf<uint32_t> band_prefix;
+  DevBuf<uint32_t> tile_spill;  // spilled neighbour-list rows of the tiled kernel, per workgroup
   int tile_spill_rows = -1;        // -1: fill the 64-entry mask (64 - list_cap); CS_TILE_SPILL_ROWS
 
   // streaming agents view (cs_snapshot_request / _acquire): two buffers, a copy stream
   struct Snapshot {
-    cs_snapshot_record* dev = nullptr;
-    cs_snapshot_record* host = nullptr;  // pinned
-    uint32_t* count_dev = nullptr;
-    uint32_t* count_host = nullptr;  // pinned
+    DevBuf<cs_snapshot_record> dev;
+    PinnedBuf<cs_snapshot_record> host;
+    DevBuf<uint32_t> count_dev;
+    PinnedBuf<uint32_t> count_host;
     uint64_t cap = 0;
     hipEvent_t gathered = nullptr, copied = nullptr;
     bool in_flight = false;
@@ -234,29 +232,31 @@ struct cs_engine {
     if (!s.gathered) {
       HIP_OK(hipEventCreateWithFlags(&s.gathered, hipEventDisableTiming));
       HIP_OK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-      HIP_OK(hipMalloc(&s.count_dev, sizeof(uint32_t)));
-      HIP_OK(hipHostMalloc(&s.count_host, sizeof(uint32_t)));
+      HIP_OK(s.count_dev.alloc(1));
+      HIP_OK(s.count_host.alloc(1));
     }
     if (s.in_flight) HIP_OK(hipEventSynchronize(s.copied));  // its previous transfer still owns the buffer
     const uint64_t need = std::max<uint64_t>(n_slots, 1);
     if (need > s.cap) {
-      hipFree(s.dev);
-      hipHostFree(s.host);
-      s.cap = need + need / 4 + 1024;
-      HIP_OK(hipMalloc(&s.dev, s.cap * sizeof(cs_snapshot_record)));
-      HIP_OK(hipHostMalloc(&s.host, s.cap * sizeof(cs_snapshot_record)));
+      s.cap = 0;
+      s.dev.release();
+      s.host.release();
+      const uint64_t ncap = need + need / 4 + 1024;
+      HIP_OK(s.dev.alloc(ncap));
+      HIP_OK(s.host.alloc(ncap));
+      s.cap = ncap;
     }
-    HIP_OK(hipMemsetAsync(s.count_dev, 0, sizeof(uint32_t), stream));
+    HIP_OK(hipMemsetAsync(s.count_dev.get(), 0, sizeof(uint32_t), stream));
     if (n_slots)
       hipLaunchKernelGGL(k_snapshot, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, gdev, buf[cur],
-                         n_slots, grid.offset_x, grid.offset_y, grid.cell_size, s.dev, (uint32_t)s.cap,
-                         s.count_dev, ext_tab_dev[0], (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base);
+                         n_slots, grid.offset_x, grid.offset_y, grid.cell_size, s.dev.get(), (uint32_t)s.cap,
+                         s.count_dev.get(), ext_tab_dev[0].get(), (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base);
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(s.gathered, stream));
     HIP_OK(hipStreamWaitEvent(copy_stream, s.gathered, 0));
-    HIP_OK(hipMemcpyAsync(s.count_host, s.count_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, copy_stream));
+    HIP_OK(hipMemcpyAsync(s.count_host.get(), s.count_dev.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, copy_stream));
     if (n_slots)
-      HIP_OK(hipMemcpyAsync(s.host, s.dev, (size_t)n_slots * sizeof(cs_snapshot_record),
+      HIP_OK(hipMemcpyAsync(s.host.get(), s.dev.get(), (size_t)n_slots * sizeof(cs_snapshot_record),
                             hipMemcpyDeviceToHost, copy_stream));
     HIP_OK(hipEventRecord(s.copied, copy_stream));
     // the step kernels that follow on `stream` do not touch s.dev; the next request that wants
@@ -286,8 +286,8 @@ struct cs_engine {
       }
       s.in_flight = false;
     }
-    *out = s.host;
-    *n = std::min<uint64_t>(*s.count_host, s.cap);
+    *out = s.host.get();
+    *n = std::min<uint64_t>(*s.count_host.get(), s.cap);
     if (step_index) *step_index = s.step_index;
     return 0;
   }
@@ -301,11 +301,10 @@ struct cs_engine {
   };
   std::vector<LpCallback> lp_callbacks;  // by local-planner handle, like lp_params
   bool any_callback_lp = false;          // some group's local planner is host code: evaluated each step (slow path)
-  float2* lp_vel = nullptr;              // per slot of the sorted arrays: recommended velocity out, the planner's answer in
+  DevBuf<float2> lp_vel;                 // per slot of the sorted arrays: recommended velocity out, the planner's answer in
   std::vector<cs_hlp_desc> hlps;
   std::vector<HostGroup> groups;
-  GroupDev* groups_dev = nullptr;
-  size_t groups_dev_cap = 0;
+  DevBuf<GroupDev> groups_dev;
   bool groups_dirty = true;
   bool any_callback_hlp = false;        // a planner needs set_target / remove events on the host
   bool any_velocity_callback = false;   // a planner is asked for velocities on the host each step
@@ -314,8 +313,7 @@ struct cs_engine {
   // kernels read pref[i], which k_hlp_field has filled; on the host the planner is a kind of its own and sets none of the
   // flags above.
   std::map<uint32_t, HostHlpField> hlp_fields;  // by planner handle
-  HlpFieldDev* hlp_field_tab = nullptr;         // device, one entry per planner handle
-  size_t hlp_field_tab_cap = 0;
+  DevBuf<HlpFieldDev> hlp_field_tab;            // device, one entry per planner handle
   uint32_t hlp_field_tab_n = 0;                 // entries of it that were uploaded
   bool hlp_fields_dirty = false;     // a field was registered since the table was uploaded
   bool any_field_hlp = false;        // some group's planner is a field: k_hlp_field runs every step
@@ -339,23 +337,9 @@ struct cs_engine {
     return hlp_field_ns;
   }
   uint64_t hlp_field_bytes() const {
-    uint64_t b = hlp_field_tab_cap * sizeof(HlpFieldDev);
+    uint64_t b = hlp_field_tab.bytes();
     for (const auto& kv : hlp_fields) b += (uint64_t)kv.second.d.nx * kv.second.d.ny * sizeof(float2);
     return b;
-  }
-  void free_hlp_fields() {
-    hlp_field_time_read();
-    for (auto& kv : hlp_fields) {
-      if (kv.second.stage_busy) hipEventSynchronize(kv.second.staged);
-      hipFree(kv.second.data);
-      if (kv.second.stage) hipHostFree(kv.second.stage);
-      if (kv.second.staged) hipEventDestroy(kv.second.staged);
-    }
-    hlp_fields.clear();
-    hipFree(hlp_field_tab);
-    hlp_field_tab = nullptr;
-    hlp_field_tab_cap = 0;
-    hlp_field_tab_n = 0;
   }
 
   // CS_HLP_ROUTE: the route book of RMFPlanner (rmf/mod.rs:83-94).  Routes are planned on the host
@@ -373,34 +357,28 @@ struct cs_engine {
   std::map<RouteKey, uint32_t> route_by_location;  // route_plans_by_location, rmf/mod.rs:90
   std::vector<uint2> route_desc_host;
   std::vector<double> route_xy_host;
-  uint2* route_desc_dev = nullptr;
-  double* route_xy_dev = nullptr;
-  size_t route_desc_cap = 0, route_xy_cap = 0;
+  DevBuf<uint2> route_desc_dev;
+  DevBuf<double> route_xy_dev;
   bool routes_dirty = false;
-  RouteBookEntry* route_book_dev = nullptr;
+  DevBuf<RouteBookEntry> route_book_dev;
   uint32_t route_book_size = 0;  // slots (a power of two), 0 = no table yet
-  double* hlp_scale_dev = nullptr;
-  size_t hlp_scale_cap = 0;
+  DevBuf<double> hlp_scale_dev;
   // tile engines: set_target calls of the last step that missed the route book.  The host merges the
   // misses of all tiles and has every tile plan them in the same order (cs_route_resolve), so that
   // route numbers, which travel in halo records, mean the same thing everywhere.
   std::vector<cs_route_miss> route_misses;
   std::vector<uint2> route_pending;  // (slot in buf[cur], entry) assignments not yet on the device
   uint32_t spawn_first_slot = 0;     // slot of this step's first spawned agent (before the re-sort)
-  uint2* route_pending_dev = nullptr;
-  size_t route_pending_cap = 0;
+  DevBuf<uint2> route_pending_dev;
 
   // source-sinks: slot == handle (registry.rs:16-21 hands out ascending integers)
   std::vector<HostSink> sinks;
-  SinkDev* sinks_dev = nullptr;
-  double* waypoints_dev = nullptr;
-  uint32_t* src_cell_start = nullptr;
-  uint32_t* src_sorted = nullptr;
-  uint32_t* src_occupied = nullptr;
-  uint32_t* want_dev = nullptr;
-  uint32_t* want_host = nullptr;  // pinned: the H2D copy of a step may still be in flight at return
-  uint32_t* spawned_slots_dev = nullptr;
-  uint32_t* spawn_scratch = nullptr;  // id of the step's first spawn + spawns per block of sinks
+  DevBuf<SinkDev> sinks_dev;
+  DevBuf<double> waypoints_dev;
+  DevBuf<uint32_t> src_cell_start, src_sorted, src_occupied, want_dev;
+  PinnedBuf<uint32_t> want_host;  // pinned: the H2D copy of a step may still be in flight at return
+  DevBuf<uint32_t> spawned_slots_dev;
+  DevBuf<uint32_t> spawn_scratch;  // id of the step's first spawn + spawns per block of sinks
   std::vector<uint32_t> want_on_device;  // what want_dev holds
   bool sinks_dirty = true;
   uint32_t n_live_sinks = 0;
@@ -409,22 +387,29 @@ struct cs_engine {
   uint32_t slots_added = 0;              // tile: slots appended (upper bound) since the last step kernel
   bool spawn_on_device = false;          // ... through cs_spawn_probe_dev/commit_dev: ids are handed out on the device
   uint32_t n_owned_sinks = 0;            // sinks whose source this tile owns (upper bound of its spawns per step)
-  SpawnRecord* spawn_rec_dev = nullptr;
-  uint32_t spawn_rec_cap = 0;
-  uint32_t* find_dev = nullptr;  // cs_remove_agent: (slot, meta) of the id looked up on the device
-  void* query_scratch = nullptr;  // device scratch of the batch spatial queries (grown as needed, never shrunk)
-  size_t query_scratch_bytes = 0;
-  int* step_flags_dev = nullptr;  // cs_tile_step_rccl: the spawn flags of the step
-  size_t step_flags_cap = 0;
+  DevBuf<SpawnRecord> spawn_rec_dev;
+  DevBuf<uint32_t> find_dev;  // cs_remove_agent: (slot, meta) of the id looked up on the device
+  DevBytes query_scratch;  // device scratch of the batch spatial queries (grown as needed, never shrunk)
+  DevBytes write_scratch;  // device scratch of the by-id calls: cs_write_agents, cs_read_agents_by_id, cs_remove_agents
+                           // (grown as needed, never shrunk: cs_agent_write.hip.inc)
+  // the selections' view of the planner groups (cs_select.hip.inc): refreshed inside a selection when a group was added
+  // since, with a flag of its own, so that a selection leaves groups_dirty and the step's tables alone
+  DevBuf<SelGroupDev> sel_groups_dev;
+  bool sel_groups_dirty = true;
+  // the raster of cs_agent_field (cs_field.hip.inc): grown to the largest raster asked for, never shrunk
+  DevBytes field_scratch;
+  // the rasters of cs_flow_field_solve (cs_flow_solve.hip.inc): grown to the largest solve asked for, never shrunk
+  DevBytes flow_scratch;
+  // the lists of cs_close_pairs, cs_agent_clusters and cs_agent_neighbours (PairsScratch, cs_near.hip.inc): kept while
+  // they need at most PAIRS_SCRATCH_KEEP bytes; a larger list is allocated for its call and freed before it returns
+  DevBytes pairs_scratch;
+  DevBuf<int> step_flags_dev;  // cs_tile_step_rccl: the spawn flags of the step
   uint32_t step_colls = 0;        // cs_tile_step_rccl: the collectives its last call issued (bit 0 exchange, bit 1 flags)
   int reserve_step_flags(size_t ns) {
-    if (ns <= step_flags_cap) return 0;
+    if (ns <= step_flags_dev.count()) return 0;
     HIP_OK(hipStreamSynchronize(stream));
-    hipFree(step_flags_dev);
-    step_flags_dev = nullptr;
-    step_flags_cap = ns * 2 + 64;
-    HIP_OK(hipMalloc(&step_flags_dev, step_flags_cap * sizeof(int)));
-    HIP_OK(hipMemsetAsync(step_flags_dev, 0, step_flags_cap * sizeof(int), stream));
+    HIP_OK(step_flags_dev.alloc(ns * 2 + 64));
+    HIP_OK(hipMemsetAsync(step_flags_dev.get(), 0, step_flags_dev.bytes(), stream));
     return 0;
   }
 
@@ -438,10 +423,8 @@ struct cs_engine {
   uint64_t id_limit = CS_ID_LIMIT;  // device ids stay below it (CS_DEVICE_ID_LIMIT lowers it under the flag)
   std::vector<uint64_t> ext_of;     // external ids of the agents alive at the last renumbering, ascending
   uint64_t dev_base = 0, ext_base = 0;
-  uint64_t* ext_tab_dev[2] = {nullptr, nullptr};  // [0]: ext_of on the device (k_snapshot), [1]: the next one
-  size_t ext_tab_cap[2] = {0, 0};
-  uint32_t* ids_scratch = nullptr;  // the renumbering's sort: two key arrays, the digit histogram, the live count
-  size_t ids_scratch_words = 0;
+  DevBuf<uint64_t> ext_tab_dev[2];  // [0]: ext_of on the device (k_snapshot), [1]: the next one
+  DevBuf<uint32_t> ids_scratch;  // the renumbering's sort: two key arrays, the digit histogram, the live count
   uint64_t n_renumberings = 0;
   uint64_t renumber_ns = 0;  // host wall time inside the renumberings (CS_STAT_RENUMBER_NS)
   uint64_t ext_id(uint64_t d) const {
@@ -472,7 +455,7 @@ struct cs_engine {
   // kTileAsync steps remains for the error counters (at 4 steps it cost 6 us per step).
   uint32_t kTileAsync = 32;
   static constexpr uint32_t kPeek = 16;
-  unsigned long long* peek_host = nullptr;  // pinned; the device writes through the same pointer
+  PinnedBuf<unsigned long long> peek_host;  // pinned; the device writes through the same pointer
   uint64_t peek_mark[kPeek] = {};  // slots_added_total when step (seq % kPeek) was launched
   uint32_t peek_seq = 0, peek_seen = 0;
   uint64_t slots_added_total = 0;  // every slot ever appended to buf[cur] outside the step kernel
@@ -494,11 +477,11 @@ struct cs_engine {
   uint32_t flight_n = 0;
   void flight_launched(uint32_t seq) { flight_seq[flight_n++ % (kFlight + 1)] = seq; }
   int flight_throttle() {
-    if (!peek_host || flight_n < kFlight) return 0;
+    if (!peek_host.get() || flight_n < kFlight) return 0;
     const uint32_t target = flight_seq[(flight_n - kFlight) % (kFlight + 1)];
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spin = 0;; ++spin) {
-      const uint32_t seen = (uint32_t)(*reinterpret_cast<volatile unsigned long long*>(peek_host) >> 32);
+      const uint32_t seen = (uint32_t)(*reinterpret_cast<volatile unsigned long long*>(peek_host.get()) >> 32);
       if ((int32_t)(seen - target) >= 0) return 0;
       if ((spin & 63u) == 63u) std::this_thread::yield();  // (RCCL's proxy threads and the other ranks want the core too)
       if ((spin & 1023u) == 1023u &&
@@ -510,8 +493,8 @@ struct cs_engine {
   }
   // takes what has arrived (never waits)
   void peek_poll() {
-    if (!peek_host) return;
-    const unsigned long long v = *reinterpret_cast<volatile unsigned long long*>(peek_host);
+    if (!peek_host.get()) return;
+    const unsigned long long v = *reinterpret_cast<volatile unsigned long long*>(peek_host.get());
     const uint32_t seq = (uint32_t)(v >> 32);
     if (seq == 0 || seq == peek_seen || peek_seq - seq >= kPeek) return;  // nothing new (or too old to have its mark)
     peek_seen = seq;
@@ -523,11 +506,11 @@ struct cs_engine {
   // those of the steps before it.  Non-zero = the next cs_step reads the counters the blocking way and fails
   // (a few steps after the event, where the periodic read alone would take up to kTileAsync steps).
   bool peek_errors() const {
-    return peek_host && *reinterpret_cast<volatile unsigned long long*>(peek_host + 1) != 0ull;
+    return peek_host.get() && *reinterpret_cast<volatile unsigned long long*>(peek_host.get() + 1) != 0ull;
   }
   // The third pinned word: Counters::mesh_fail_step as the last step kernel that has started found it (cs_mesh).
   uint32_t peek_mesh_fail() const {
-    return peek_host ? (uint32_t)*reinterpret_cast<volatile unsigned long long*>(peek_host + 2) : 0u;
+    return peek_host.get() ? (uint32_t)*reinterpret_cast<volatile unsigned long long*>(peek_host.get() + 2) : 0u;
   }
   // CS_CFG_TILE_OVERLAP, how: true (default since round 5) = ONE launch with the border windows first and the exchange of
   // the next step behind a one-wave kernel that waits for them (no split-launch cost: k_step_tiled, TileCfg::split == 2);
@@ -554,20 +537,6 @@ struct cs_engine {
   uint64_t prof_n[CS_K_COUNT] = {};
 
   // ---- memory ----
-  int alloc_arrays(AgentArrays& a, uint64_t n) {
-    HIP_OK(hipMalloc(&a.off, n * sizeof(float2)));
-    HIP_OK(hipMalloc(&a.vel, n * sizeof(float2)));
-    HIP_OK(hipMalloc(&a.id, n * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&a.cell, n * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&a.meta, n * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&a.rank, n * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&a.route, n * sizeof(uint32_t)));
-    return 0;
-  }
-  void free_arrays(AgentArrays& a) {
-    hipFree(a.off); hipFree(a.vel); hipFree(a.id); hipFree(a.cell); hipFree(a.meta); hipFree(a.rank); hipFree(a.route);
-    a = AgentArrays{};
-  }
   // the agent arrays as the kernels see them: no route column while no route planner exists
   AgentArrays view(int b) const {
     AgentArrays a = buf[b];
@@ -584,8 +553,9 @@ struct cs_engine {
     }
     HIP_OK(hipStreamSynchronize(stream));
     for (int b = 0; b < 2; ++b) {
-      AgentArrays na{};
-      if (int rc = alloc_arrays(na, ncap)) return rc;
+      AgentBuf mem;
+      HIP_OK(mem.alloc(ncap));
+      const AgentArrays na = mem.view();
       if (cap && b == cur && n_slots) {
         HIP_OK(hipMemcpy(na.off, buf[b].off, n_slots * sizeof(float2), hipMemcpyDeviceToDevice));
         HIP_OK(hipMemcpy(na.vel, buf[b].vel, n_slots * sizeof(float2), hipMemcpyDeviceToDevice));
@@ -595,28 +565,25 @@ struct cs_engine {
         HIP_OK(hipMemcpy(na.rank, buf[b].rank, n_slots * sizeof(uint32_t), hipMemcpyDeviceToDevice));
         HIP_OK(hipMemcpy(na.route, buf[b].route, n_slots * sizeof(uint32_t), hipMemcpyDeviceToDevice));
       }
-      free_arrays(buf[b]);
+      buf_mem[b] = std::move(mem);  // (frees the old columns)
       buf[b] = na;
     }
-    hipFree(pref);
-    HIP_OK(hipMalloc(&pref, ncap * sizeof(float2)));
-    HIP_OK(hipMemset(pref, 0, ncap * sizeof(float2)));
-    hipFree(lp_vel);
-    lp_vel = nullptr;  // (allocated by the first step that has a host local planner)
-    hipFree(destroyed);
+    HIP_OK(pref.alloc(ncap));
+    HIP_OK(hipMemset(pref.get(), 0, ncap * sizeof(float2)));
+    lp_vel.release();  // (allocated by the first step that has a host local planner)
+    destroyed_cap = wp_events_cap = 0;
+    HIP_OK(destroyed.alloc(ncap));
     destroyed_cap = (uint32_t)ncap;
-    HIP_OK(hipMalloc(&destroyed, (uint64_t)destroyed_cap * sizeof(uint2)));
-    hipFree(wp_events);
+    HIP_OK(wp_events.alloc(ncap));
     wp_events_cap = (uint32_t)ncap;
-    HIP_OK(hipMalloc(&wp_events, (uint64_t)wp_events_cap * sizeof(WpEvent)));
     // band windows: at most 2 * agents / tile_target + one per band (the builder keeps every band
     // within that); one-row strips: agents / 256 + one per row
     if (int rc = alloc_window_arrays((uint32_t)(ncap / 32 + ncells / std::max<uint64_t>(nx, 1) + 8))) return rc;
-    if (!n_blocks_dev) {
-      HIP_OK(hipMalloc(&n_blocks_dev, 2 * sizeof(uint32_t)));  // [0] windows, [1] border windows
-      HIP_OK(hipMalloc(&n_blocks_back, 2 * sizeof(uint32_t)));
-      HIP_OK(hipMemset(n_blocks_dev, 0, 2 * sizeof(uint32_t)));
-      HIP_OK(hipMemset(n_blocks_back, 0, 2 * sizeof(uint32_t)));
+    if (!n_blocks_dev.get()) {
+      HIP_OK(n_blocks_dev.alloc(2));  // [0] windows, [1] border windows
+      HIP_OK(n_blocks_back.alloc(2));
+      HIP_OK(hipMemset(n_blocks_dev.get(), 0, 2 * sizeof(uint32_t)));
+      HIP_OK(hipMemset(n_blocks_back.get(), 0, 2 * sizeof(uint32_t)));
     }
     cap = ncap;
     return 0;
@@ -827,16 +794,13 @@ struct cs_engine {
           any_callback_hlp = true;
       }
     }
-    if (g.size() > groups_dev_cap) {  // (grows by doubling: 200,000 source-sinks are 200,000 groups)
+    if (g.size() > groups_dev.count()) {  // (grows by doubling: 200,000 source-sinks are 200,000 groups)
       HIP_OK(hipStreamSynchronize(stream));
-      hipFree(groups_dev);
-      groups_dev = nullptr;
-      groups_dev_cap = std::max<size_t>(1024, 2 * g.size());
-      HIP_OK(hipMalloc(&groups_dev, groups_dev_cap * sizeof(GroupDev)));
+      HIP_OK(groups_dev.alloc(std::max<size_t>(1024, 2 * g.size())));
       epi_valid[0] = epi_valid[1] = false;  // (the step kernels' context names the table)
     }
     if (!g.empty())
-      HIP_OK(hipMemcpyAsync(groups_dev, g.data(), g.size() * sizeof(GroupDev), hipMemcpyHostToDevice,
+      HIP_OK(hipMemcpyAsync(groups_dev.get(), g.data(), g.size() * sizeof(GroupDev), hipMemcpyHostToDevice,
                             stream));
     HIP_OK(hipStreamSynchronize(stream));
     groups_dirty = false;
@@ -886,35 +850,32 @@ struct cs_engine {
     n_owned_sinks = 0;  // (+ the sources in the ring: their spawns arrive as ghosts)
     for (const SinkDev& d : sd)
       if (d.src_cell != CS_INVALID_CELL || d.ghost_cell != CS_INVALID_CELL) n_owned_sinks += 1;
-    hipFree(sinks_dev); hipFree(waypoints_dev); hipFree(src_sorted); hipFree(src_occupied);
-    hipFree(want_dev); hipFree(spawned_slots_dev); hipFree(spawn_scratch); hipHostFree(want_host);
-    want_host = nullptr;
-    sinks_dev = nullptr; waypoints_dev = nullptr; src_sorted = nullptr; src_occupied = nullptr;
-    want_dev = nullptr; spawned_slots_dev = nullptr; spawn_scratch = nullptr;
+    sinks_dev.release(); waypoints_dev.release(); src_sorted.release(); src_occupied.release();
+    want_dev.release(); spawned_slots_dev.release(); spawn_scratch.release(); want_host.release();
     want_on_device.clear();
     size_t nalloc = std::max<size_t>(ns, 1);
-    HIP_OK(hipMalloc(&sinks_dev, nalloc * sizeof(SinkDev)));
-    HIP_OK(hipMalloc(&waypoints_dev, std::max<size_t>(wps.size(), 2) * sizeof(double)));
-    HIP_OK(hipMalloc(&src_sorted, nalloc * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&src_occupied, nalloc * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&want_dev, nalloc * sizeof(uint32_t)));
-    HIP_OK(hipHostMalloc(&want_host, (size_t)kWantRing * nalloc * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&spawned_slots_dev, nalloc * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&spawn_scratch, (nalloc / SPAWN_BLOCK + 3) * sizeof(uint32_t)));
-    HIP_OK(hipMemset(src_occupied, 0, nalloc * sizeof(uint32_t)));
-    if (ns) HIP_OK(hipMemcpy(sinks_dev, sd.data(), ns * sizeof(SinkDev), hipMemcpyHostToDevice));
+    HIP_OK(sinks_dev.alloc(nalloc));
+    HIP_OK(waypoints_dev.alloc(std::max<size_t>(wps.size(), 2)));
+    HIP_OK(src_sorted.alloc(nalloc));
+    HIP_OK(src_occupied.alloc(nalloc));
+    HIP_OK(want_dev.alloc(nalloc));
+    HIP_OK(want_host.alloc((size_t)kWantRing * nalloc));
+    HIP_OK(spawned_slots_dev.alloc(nalloc));
+    HIP_OK(spawn_scratch.alloc(nalloc / SPAWN_BLOCK + 3));
+    HIP_OK(hipMemset(src_occupied.get(), 0, nalloc * sizeof(uint32_t)));
+    if (ns) HIP_OK(hipMemcpy(sinks_dev.get(), sd.data(), ns * sizeof(SinkDev), hipMemcpyHostToDevice));
     if (!wps.empty())
-      HIP_OK(hipMemcpy(waypoints_dev, wps.data(), wps.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(waypoints_dev.get(), wps.data(), wps.size() * sizeof(double), hipMemcpyHostToDevice));
     // static source grid: sources sorted by cell + per-cell start
     std::sort(by_cell.begin(), by_cell.end());
     std::vector<uint32_t> start(ncells + 1, 0), sorted_slots(by_cell.size());
     for (auto& bc : by_cell) start[bc.first + 1]++;
     for (uint64_t c = 0; c < ncells; ++c) start[c + 1] += start[c];
     for (size_t k = 0; k < by_cell.size(); ++k) sorted_slots[k] = by_cell[k].second;
-    if (!src_cell_start) HIP_OK(hipMalloc(&src_cell_start, (ncells + 1) * sizeof(uint32_t)));
-    HIP_OK(hipMemcpy(src_cell_start, start.data(), (ncells + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!src_cell_start.get()) HIP_OK(src_cell_start.alloc(ncells + 1));
+    HIP_OK(hipMemcpy(src_cell_start.get(), start.data(), (ncells + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!sorted_slots.empty())
-      HIP_OK(hipMemcpy(src_sorted, sorted_slots.data(), sorted_slots.size() * sizeof(uint32_t),
+      HIP_OK(hipMemcpy(src_sorted.get(), sorted_slots.data(), sorted_slots.size() * sizeof(uint32_t),
                        hipMemcpyHostToDevice));
     sinks_dirty = false;
     occ_valid = false;
@@ -925,10 +886,10 @@ struct cs_engine {
   // ---- histogram of buf[cur] (only when the one kept by the step kernel is stale) ----
   int recount() {
     if (hist_valid) return 0;
-    HIP_OK(hipMemsetAsync(cell_count, 0, (ncells + 1) * sizeof(uint32_t), stream));
+    HIP_OK(hipMemsetAsync(cell_count.get(), 0, (ncells + 1) * sizeof(uint32_t), stream));
     if (n_slots)
       hipLaunchKernelGGL(k_count, dim3((n_slots + 255) / 256), dim3(256), 0, stream, buf[cur], 0u,
-                         n_slots, cell_count, ctr, gdev.tile);
+                         n_slots, cell_count.get(), ctr.get(), gdev.tile);
     HIP_OK(hipGetLastError());
     hist_valid = true;
     return 0;
@@ -970,7 +931,7 @@ struct cs_engine {
   uint32_t windows_keep_max_agents = 300000, windows_slack_pct = 10;  // (measured: pays up to ~250k slots, even beyond)
   bool windows_valid = false;
   bool scan_onepass = true;  // CS_SCAN_ONEPASS=0: the two-launch scan
-  unsigned long long* scan_tile_sums = nullptr;
+  DevBuf<unsigned long long> scan_tile_sums;
   uint32_t scan_seq = 0;
   uint32_t debug_sort_every = 0, debug_sort_phase = 0, debug_sorted_slots = 0;  // CS_DEBUG_SORT_EVERY (measurement only: rebuild)
   bool debug_sorted_once = false;
@@ -978,8 +939,8 @@ struct cs_engine {
   uint32_t scan_ticket_base = 0;  // tickets handed out by all earlier launches of k_scan_onepass (the word behind the sums)
   uint32_t kept_agents_cap = 0;  // the staging slots per window the kept list was cut for (sticky: see step())
   uint32_t windows_bound = 0;  // the most windows the kept arrays can hold: band_windows_max of the step that cut them
-  BlockDesc* blk_desc_back = nullptr;
-  uint32_t* n_blocks_back = nullptr;
+  DevBuf<BlockDesc> blk_desc_back;
+  DevBuf<uint32_t> n_blocks_back;
   struct WindowsKey {
     uint32_t ncells, nx, own_x0, own_x1, own_y0, own_y1, org_x, org_y, h, desc_cap, rows, target, stage_cap, split;
     const void* desc;
@@ -987,13 +948,13 @@ struct cs_engine {
   } windows_key{};
   // (both descriptor arrays, and both window counters, are allocated together)
   int alloc_window_arrays(uint32_t cap_each) {
-    hipFree(blk_desc);
-    hipFree(blk_desc_back);
-    blk_desc = blk_desc_back = nullptr;
-    blk_desc_cap = cap_each;
-    HIP_OK(hipMalloc(&blk_desc, (uint64_t)blk_desc_cap * sizeof(BlockDesc)));
-    HIP_OK(hipMalloc(&blk_desc_back, (uint64_t)blk_desc_cap * sizeof(BlockDesc)));
+    blk_desc.release();
+    blk_desc_back.release();
+    blk_desc_cap = 0;
     windows_valid = false;
+    HIP_OK(blk_desc.alloc(cap_each));
+    HIP_OK(blk_desc_back.alloc(cap_each));
+    blk_desc_cap = cap_each;
     return 0;
   }
   uint64_t n_steps_on_kept_windows = 0;
@@ -1032,7 +993,7 @@ struct cs_engine {
     // the slots every window owns, per owned row (a window of whole cells owns its cells' members): they must tile the
     // row's owned slots exactly once
     std::vector<uint32_t> cs((size_t)ncells + 1u);
-    HIP_OK(hipMemcpy(cs.data(), cell_start, ((size_t)ncells + 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(cs.data(), cell_start.get(), ((size_t)ncells + 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     const uint32_t own_rows = gdev.own_x1 - gdev.own_x0;
     std::vector<std::vector<std::pair<uint32_t, uint32_t>>> runs(own_rows);
     for (uint32_t k = 0; k < cnt[0]; ++k) {
@@ -1135,8 +1096,8 @@ struct cs_engine {
     // windows still fit); it prices the most a Verlet-style reuse of the sort could save, nothing else uses it.
     if (debug_sort_every > 1 && !tile && n_live_sinks == 0 && debug_sorted_once && !keep_windows && n_slots == debug_sorted_slots &&
         (++debug_sort_phase % debug_sort_every) != 0) {
-      HIP_OK(hipMemsetAsync(cell_count, 0, (size_t)ncells * sizeof(uint32_t), stream));  // (what the scan does while it reads)
-      HIP_OK(hipMemsetAsync(&ctr->n_destroyed, 0, 6 * sizeof(uint32_t), stream));        // n_destroyed .. n_wp_events
+      HIP_OK(hipMemsetAsync(cell_count.get(), 0, (size_t)ncells * sizeof(uint32_t), stream));  // (what the scan does while it reads)
+      HIP_OK(hipMemsetAsync(&ctr.get()->n_destroyed, 0, 6 * sizeof(uint32_t), stream));        // n_destroyed .. n_wp_events
       bands_built = bands_were_built;
       sorted = true;
       hist_valid = false;
@@ -1145,25 +1106,25 @@ struct cs_engine {
     debug_sorted_once = true;
     debug_sorted_slots = n_slots;
     prof_begin(CS_K_SCAN);
-    uint32_t* const scan_clears = (keep_windows || windows_valid) ? n_blocks_back : n_blocks_dev;
+    uint32_t* const scan_clears = (keep_windows || windows_valid) ? n_blocks_back.get() : n_blocks_dev.get();
     if (scan_onepass && n_scan_blocks <= SCAN_ONEPASS_MAX_BLOCKS) {
-      if (!scan_tile_sums) {  // (one 64-bit word per tile: sequence number | sum; sequence numbers start at 1; behind
+      if (!scan_tile_sums.get()) {  // (one 64-bit word per tile: sequence number | sum; sequence numbers start at 1; behind
                               //  them the ticket counter)
-        HIP_OK(hipMalloc(&scan_tile_sums, ((size_t)SCAN_ONEPASS_MAX_BLOCKS + 1) * sizeof(unsigned long long)));
-        HIP_OK(hipMemsetAsync(scan_tile_sums, 0, ((size_t)SCAN_ONEPASS_MAX_BLOCKS + 1) * sizeof(unsigned long long), stream));
+        HIP_OK(scan_tile_sums.alloc((size_t)SCAN_ONEPASS_MAX_BLOCKS + 1));
+        HIP_OK(hipMemsetAsync(scan_tile_sums.get(), 0, ((size_t)SCAN_ONEPASS_MAX_BLOCKS + 1) * sizeof(unsigned long long), stream));
         scan_ticket_base = 0;
       }
       if (++scan_seq == 0u) scan_seq = 1u;
-      hipLaunchKernelGGL(k_scan_onepass, dim3(n_scan_blocks), dim3(SCAN_BLOCK), 0, stream, cell_count, (uint32_t)ncells,
-                         cell_start, ctr, scan_clears, scan_tile_sums, scan_seq,
-                         reinterpret_cast<uint32_t*>(scan_tile_sums + SCAN_ONEPASS_MAX_BLOCKS), scan_ticket_base);
+      hipLaunchKernelGGL(k_scan_onepass, dim3(n_scan_blocks), dim3(SCAN_BLOCK), 0, stream, cell_count.get(), (uint32_t)ncells,
+                         cell_start.get(), ctr.get(), scan_clears, scan_tile_sums.get(), scan_seq,
+                         reinterpret_cast<uint32_t*>(scan_tile_sums.get() + SCAN_ONEPASS_MAX_BLOCKS), scan_ticket_base);
       scan_ticket_base += n_scan_blocks;  // (every workgroup of a launch takes exactly one ticket)
     } else {
-      hipLaunchKernelGGL(k_scan_totals, dim3(n_scan_blocks), dim3(SCAN_BLOCK), 0, stream, cell_count,
-                         (uint32_t)ncells, block_totals);
-      hipLaunchKernelGGL(k_scan_bases, dim3(1), dim3(SCAN_BASES_BLOCK), 0, stream, block_totals, n_scan_blocks);
-      hipLaunchKernelGGL(k_scan_apply, dim3(n_scan_blocks), dim3(SCAN_BLOCK), 0, stream, cell_count,
-                         (uint32_t)ncells, block_totals, cell_start, ctr, scan_clears);
+      hipLaunchKernelGGL(k_scan_totals, dim3(n_scan_blocks), dim3(SCAN_BLOCK), 0, stream, cell_count.get(),
+                         (uint32_t)ncells, block_totals.get());
+      hipLaunchKernelGGL(k_scan_bases, dim3(1), dim3(SCAN_BASES_BLOCK), 0, stream, block_totals.get(), n_scan_blocks);
+      hipLaunchKernelGGL(k_scan_apply, dim3(n_scan_blocks), dim3(SCAN_BLOCK), 0, stream, cell_count.get(),
+                         (uint32_t)ncells, block_totals.get(), cell_start.get(), ctr.get(), scan_clears);
     }
     // (kept windows: the scan clears the counters of the array the builder workgroups of this step fill.  A sort BETWEEN
     // two steps, for a query or a read, must leave the windows the next step will run on alone: windows_valid is still
@@ -1173,13 +1134,13 @@ struct cs_engine {
     if (n_slots && (bands || keep_windows)) {
       const uint32_t sb = (n_slots + 255) / 256;
       hipLaunchKernelGGL(k_scatter_and_bands, dim3(sb + bands), dim3(256), 0, stream, view(cur), view(cur ^ 1),
-                         n_slots, cell_start, bands, gdev, band_rows, band_target ? band_target : tile_target, band_h,
+                         n_slots, cell_start.get(), bands, gdev, band_rows, band_target ? band_target : tile_target, band_h,
                          band_stage_cap, tile_max_cols(band_h), split_margin(), cover ? 1u : 0u,
-                         band_prefix, blk_desc, blk_desc_cap, n_blocks_dev, ctr);
+                         band_prefix.get(), blk_desc.get(), blk_desc_cap, n_blocks_dev.get(), ctr.get());
       bands_built = true;
     } else if (n_slots) {
       hipLaunchKernelGGL(k_scatter, dim3((n_slots + 255) / 256), dim3(256), 0, stream, view(cur),
-                         view(cur ^ 1), n_slots, cell_start, ctr, gdev.tile, (uint32_t)ncells);
+                         view(cur ^ 1), n_slots, cell_start.get(), ctr.get(), gdev.tile, (uint32_t)ncells);
     }
     prof_end();
     HIP_OK(hipGetLastError());
@@ -1191,10 +1152,10 @@ struct cs_engine {
 
   int mark_occupancy() {
     if (occ_valid || n_live_sinks == 0) return 0;
-    HIP_OK(hipMemsetAsync(src_occupied, 0, std::max<size_t>(sinks.size(), 1) * sizeof(uint32_t), stream));
+    HIP_OK(hipMemsetAsync(src_occupied.get(), 0, std::max<size_t>(sinks.size(), 1) * sizeof(uint32_t), stream));
     if (n_slots)
       hipLaunchKernelGGL(k_mark_sources, dim3((n_slots + 255) / 256), dim3(256), 0, stream, gdev,
-                         buf[cur], n_slots, sinks_dev, src_cell_start, src_sorted, src_occupied, ctr);
+                         buf[cur], n_slots, sinks_dev.get(), src_cell_start.get(), src_sorted.get(), src_occupied.get(), ctr.get());
     HIP_OK(hipGetLastError());
     occ_valid = true;
     return 0;
@@ -1210,9 +1171,9 @@ struct cs_engine {
       "the window builder made more band windows than the step kernel's launch was sized for: some agents were not stepped "
       "(band_windows_max is a bound on the builder's output; please report the scene)";
   int read_counters(Counters* out) {
-    HIP_OK(hipMemcpyAsync(ctr_host, ctr, sizeof(Counters), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(ctr_host.get(), ctr.get(), sizeof(Counters), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    *out = *ctr_host;
+    *out = *ctr_host.get();
     return 0;
   }
 
@@ -1325,11 +1286,9 @@ struct cs_engine {
   // Bring the device tables up to date: the routes, the route book (hash table) and the planners'
   // SpatialHash resolutions.  Runs before any kernel that may read them.
   int flush_route_tables() {
-    if (hlps.size() > hlp_scale_cap || (any_route_hlp && !hlp_scale_dev)) {
+    if (hlps.size() > hlp_scale_dev.count() || (any_route_hlp && !hlp_scale_dev.get())) {
       HIP_OK(hipStreamSynchronize(stream));
-      hipFree(hlp_scale_dev);
-      hlp_scale_cap = hlps.size() * 2 + 8;
-      HIP_OK(hipMalloc(&hlp_scale_dev, hlp_scale_cap * sizeof(double)));
+      HIP_OK(hlp_scale_dev.alloc(hlps.size() * 2 + 8));
       routes_dirty = true;
     }
     if (!routes_dirty) return 0;
@@ -1339,31 +1298,22 @@ struct cs_engine {
       for (size_t k = 0; k < hlps.size(); ++k)
         if (hlps[k].kind == CS_HLP_ROUTE) scale[k] = hlps[k].route_scale;
       if (!scale.empty())
-        HIP_OK(hipMemcpy(hlp_scale_dev, scale.data(), scale.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(hlp_scale_dev.get(), scale.data(), scale.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (route_desc_host.size() > route_desc_cap) {
-      hipFree(route_desc_dev);
-      route_desc_cap = route_desc_host.size() * 2;
-      HIP_OK(hipMalloc(&route_desc_dev, route_desc_cap * sizeof(uint2)));
-    }
-    if (route_xy_host.size() > route_xy_cap) {
-      hipFree(route_xy_dev);
-      route_xy_cap = route_xy_host.size() * 2;
-      HIP_OK(hipMalloc(&route_xy_dev, route_xy_cap * sizeof(double)));
-    }
+    if (route_desc_host.size() > route_desc_dev.count()) HIP_OK(route_desc_dev.alloc(route_desc_host.size() * 2));
+    if (route_xy_host.size() > route_xy_dev.count()) HIP_OK(route_xy_dev.alloc(route_xy_host.size() * 2));
     if (!route_desc_host.empty()) {
-      HIP_OK(hipMemcpy(route_desc_dev, route_desc_host.data(), route_desc_host.size() * sizeof(uint2),
+      HIP_OK(hipMemcpy(route_desc_dev.get(), route_desc_host.data(), route_desc_host.size() * sizeof(uint2),
                        hipMemcpyHostToDevice));
-      HIP_OK(hipMemcpy(route_xy_dev, route_xy_host.data(), route_xy_host.size() * sizeof(double),
+      HIP_OK(hipMemcpy(route_xy_dev.get(), route_xy_host.data(), route_xy_host.size() * sizeof(double),
                        hipMemcpyHostToDevice));
     }
     // the route book as an open-addressing table, at most half full
     uint32_t want = 64;
     while (want < 2u * route_by_location.size() + 2u) want <<= 1;
     if (want != route_book_size) {
-      hipFree(route_book_dev);
-      route_book_dev = nullptr;
-      HIP_OK(hipMalloc(&route_book_dev, (size_t)want * sizeof(RouteBookEntry)));
+      route_book_size = 0;
+      HIP_OK(route_book_dev.alloc(want));
       route_book_size = want;
     }
     std::vector<RouteBookEntry> table(route_book_size, RouteBookEntry{0, 0, 0, 0, 0u, 0u});
@@ -1373,7 +1323,7 @@ struct cs_engine {
       while (table[k].route1 != 0u) k = (k + 1u) & (route_book_size - 1u);
       table[k] = RouteBookEntry{key.sx, key.sy, key.gx, key.gy, key.hlp, kv.second + 1u};
     }
-    HIP_OK(hipMemcpy(route_book_dev, table.data(), table.size() * sizeof(RouteBookEntry), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(route_book_dev.get(), table.data(), table.size() * sizeof(RouteBookEntry), hipMemcpyHostToDevice));
     routes_dirty = false;
     return 0;
   }
@@ -1381,17 +1331,15 @@ struct cs_engine {
   // anything reorders the arrays: right after the events that produced them were handled.
   int flush_route_pending() {
     if (route_pending.empty()) return 0;
-    if (route_pending.size() > route_pending_cap) {
+    if (route_pending.size() > route_pending_dev.count()) {
       HIP_OK(hipStreamSynchronize(stream));
-      hipFree(route_pending_dev);
-      route_pending_cap = route_pending.size() * 2;
-      HIP_OK(hipMalloc(&route_pending_dev, route_pending_cap * sizeof(uint2)));
+      HIP_OK(route_pending_dev.alloc(route_pending.size() * 2));
     }
-    HIP_OK(hipMemcpy(route_pending_dev, route_pending.data(), route_pending.size() * sizeof(uint2),
+    HIP_OK(hipMemcpy(route_pending_dev.get(), route_pending.data(), route_pending.size() * sizeof(uint2),
                      hipMemcpyHostToDevice));
     const uint32_t m = (uint32_t)route_pending.size();
     hipLaunchKernelGGL(k_route_assign, dim3((m + 255u) / 256u), dim3(256), 0, stream, buf[cur].route, n_slots,
-                       route_pending_dev, m);
+                       route_pending_dev.get(), m);
     HIP_OK(hipGetLastError());
     route_pending.clear();
     return 0;
@@ -1427,7 +1375,7 @@ struct cs_engine {
         if (some[k]) pv[slots[k]] = make_float2((float)out[2 * k], (float)out[2 * k + 1]);
     }
     if (n) {
-      HIP_OK(hipMemcpyAsync(pref, pv.data(), n * sizeof(float2), hipMemcpyHostToDevice, stream));
+      HIP_OK(hipMemcpyAsync(pref.get(), pv.data(), n * sizeof(float2), hipMemcpyHostToDevice, stream));
       HIP_OK(hipStreamSynchronize(stream));
     }
     return 0;
@@ -1467,14 +1415,8 @@ struct cs_engine {
     const uint32_t n = n_slots;
     const size_t tiles_max = (n + IDS_TILE - 1u) / IDS_TILE;
     const size_t words = 2u * (size_t)n + IDS_RADIX * tiles_max + 1u;
-    if (words > ids_scratch_words) {
-      hipFree(ids_scratch);
-      ids_scratch = nullptr;
-      ids_scratch_words = 0;
-      HIP_OK(hipMalloc(&ids_scratch, words * sizeof(uint32_t)));
-      ids_scratch_words = words;
-    }
-    uint32_t* keys = ids_scratch;
+    if (words > ids_scratch.count()) HIP_OK(ids_scratch.alloc(words));
+    uint32_t* keys = ids_scratch.get();
     uint32_t* other = keys + n;
     uint32_t* hist = other + n;
     uint32_t* count_dev = hist + IDS_RADIX * tiles_max;
@@ -1499,31 +1441,24 @@ struct cs_engine {
         hipLaunchKernelGGL(k_ids_scatter, dim3(tiles), dim3(IDS_BLOCK), 0, stream, keys, other, n_live, shift, hist, tiles);
         std::swap(keys, other);
       }
-      if (ext_tab_cap[1] < n_live) {
-        hipFree(ext_tab_dev[1]);
-        ext_tab_dev[1] = nullptr;
-        ext_tab_cap[1] = 0;
-        HIP_OK(hipMalloc(&ext_tab_dev[1], (size_t)n_live * sizeof(uint64_t)));
-        ext_tab_cap[1] = n_live;
-      }
+      if (ext_tab_dev[1].count() < n_live) HIP_OK(ext_tab_dev[1].alloc(n_live));
       hipLaunchKernelGGL(k_ids_renumber, dim3((n + 255u) / 256u), dim3(256), 0, stream, buf[cur], n, keys, n_live);
-      hipLaunchKernelGGL(k_ids_table, dim3((n_live + 255u) / 256u), dim3(256), 0, stream, keys, n_live, ext_tab_dev[0],
-                         (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base, ext_tab_dev[1]);
+      hipLaunchKernelGGL(k_ids_table, dim3((n_live + 255u) / 256u), dim3(256), 0, stream, keys, n_live, ext_tab_dev[0].get(),
+                         (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base, ext_tab_dev[1].get());
       HIP_OK(hipGetLastError());
     }
     std::vector<uint64_t> tab(n_live);
     if (n_live)
-      HIP_OK(hipMemcpyAsync(tab.data(), ext_tab_dev[1], (size_t)n_live * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+      HIP_OK(hipMemcpyAsync(tab.data(), ext_tab_dev[1].get(), (size_t)n_live * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
     const uint64_t next_ext = ext_id(next_id);  // what the next allocation would have been called
     ext_of.swap(tab);
     std::swap(ext_tab_dev[0], ext_tab_dev[1]);
-    std::swap(ext_tab_cap[0], ext_tab_cap[1]);
     ext_base = next_ext;
     dev_base = 2u * (uint64_t)n_live + ((2u * (uint64_t)n_live ^ ext_base) & 1u);
     next_id = dev_base;
     const uint32_t nid = (uint32_t)next_id;
-    HIP_OK(hipMemcpy(&ctr->next_id, &nid, sizeof nid, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(&ctr.get()->next_id, &nid, sizeof nid, hipMemcpyHostToDevice));
     halo_invalidate();
     ++n_renumberings;
     renumber_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
@@ -1551,14 +1486,8 @@ struct cs_engine {
     const uint32_t n = n_slots;
     const size_t tiles_max = (n + IDS_TILE - 1u) / IDS_TILE;
     const size_t words = 2u * (size_t)n + IDS_RADIX * tiles_max + 1u;
-    if (words > ids_scratch_words) {
-      hipFree(ids_scratch);
-      ids_scratch = nullptr;
-      ids_scratch_words = 0;
-      HIP_OK(hipMalloc(&ids_scratch, words * sizeof(uint32_t)));
-      ids_scratch_words = words;
-    }
-    uint32_t* keys = ids_scratch;
+    if (words > ids_scratch.count()) HIP_OK(ids_scratch.alloc(words));
+    uint32_t* keys = ids_scratch.get();
     uint32_t* other = keys + n;
     uint32_t* hist = other + n;
     uint32_t* count_dev = hist + IDS_RADIX * tiles_max;
@@ -1585,10 +1514,10 @@ struct cs_engine {
       std::swap(keys, other);
     }
     if (int rc = ext_tab_reserve(1, n_live)) return rc;
-    hipLaunchKernelGGL(k_ids_table, dim3((n_live + 255u) / 256u), dim3(256), 0, stream, keys, n_live, ext_tab_dev[0],
-                       (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base, ext_tab_dev[1]);
+    hipLaunchKernelGGL(k_ids_table, dim3((n_live + 255u) / 256u), dim3(256), 0, stream, keys, n_live, ext_tab_dev[0].get(),
+                       (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base, ext_tab_dev[1].get());
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(out->data(), ext_tab_dev[1], (size_t)n_live * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(out->data(), ext_tab_dev[1].get(), (size_t)n_live * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
     return 0;
   }
@@ -1597,31 +1526,26 @@ struct cs_engine {
   int wide_apply_table(const std::vector<uint64_t>& all, uint64_t next_ext) {
     const uint32_t L = (uint32_t)all.size();
     if (int rc = ext_tab_reserve(1, L)) return rc;
-    if (L) HIP_OK(hipMemcpyAsync(ext_tab_dev[1], all.data(), (size_t)L * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    if (L) HIP_OK(hipMemcpyAsync(ext_tab_dev[1].get(), all.data(), (size_t)L * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
     if (n_slots && L)
       hipLaunchKernelGGL(k_ids_renumber_ext, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, buf[cur], n_slots,
-                         ext_tab_dev[0], (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base, ext_tab_dev[1], L);
+                         ext_tab_dev[0].get(), (uint32_t)ext_of.size(), (uint32_t)dev_base, ext_base, ext_tab_dev[1].get(), L);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(stream));
     ext_of = all;
     std::swap(ext_tab_dev[0], ext_tab_dev[1]);
-    std::swap(ext_tab_cap[0], ext_tab_cap[1]);
     ext_base = next_ext;
     dev_base = 2u * (uint64_t)L + ((2u * (uint64_t)L ^ ext_base) & 1u);
     next_id = dev_base;
     const uint32_t nid = (uint32_t)next_id;
-    HIP_OK(hipMemcpy(&ctr->next_id, &nid, sizeof nid, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(&ctr.get()->next_id, &nid, sizeof nid, hipMemcpyHostToDevice));
     halo_invalidate();
     ++n_renumberings;
     return 0;
   }
   int ext_tab_reserve(int k, uint32_t n) {
-    if (ext_tab_cap[k] >= n) return 0;
-    hipFree(ext_tab_dev[k]);
-    ext_tab_dev[k] = nullptr;
-    ext_tab_cap[k] = 0;
-    HIP_OK(hipMalloc(&ext_tab_dev[k], (size_t)std::max<uint32_t>(n, 1u) * sizeof(uint64_t)));
-    ext_tab_cap[k] = std::max<uint32_t>(n, 1u);
+    if (ext_tab_dev[k].count() >= n) return 0;
+    HIP_OK(ext_tab_dev[k].alloc(std::max<uint32_t>(n, 1u)));
     return 0;
   }
 
@@ -1687,11 +1611,11 @@ struct cs_engine {
       hist_valid = false;
       occ_valid = false;
       halo_invalidate();
-      HIP_OK(hipMemcpy(&ctr->n_pending, &n_slots, sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(&ctr.get()->n_pending, &n_slots, sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     {
       uint32_t nid = (uint32_t)next_id;
-      HIP_OK(hipMemcpy(&ctr->next_id, &nid, sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(&ctr.get()->next_id, &nid, sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     return rc;
   }
@@ -1739,17 +1663,17 @@ struct cs_engine {
     if (int rc = upload_sinks()) return rc;
     if (int rc = upload_groups()) return rc;
     std::memset(flags, 0, sinks.size());
-    uint32_t n_want = eval_generators(dt_seconds, want_host);
+    uint32_t n_want = eval_generators(dt_seconds, want_host.get());
     if (!n_want) return 0;
     occ_valid = false;  // ghosts arrived since the step kernel marked its own agents
     if (int rc = mark_occupancy()) return rc;
     std::vector<uint32_t> occ(sinks.size());
-    HIP_OK(hipMemcpyAsync(occ.data(), src_occupied, sinks.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+    HIP_OK(hipMemcpyAsync(occ.data(), src_occupied.get(), sinks.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
                           stream));
     HIP_OK(hipStreamSynchronize(stream));
     std::vector<SinkDev> dummy;
     for (size_t s = 0; s < sinks.size(); ++s) {
-      if (!want_host[s] || occ[s]) continue;
+      if (!want_host.get()[s] || occ[s]) continue;
       uint32_t c;
       float ox, oy;
       if (to_cell(sinks[s].d.source_x, sinks[s].d.source_y, &c, &ox, &oy) == 0) flags[s] = 1;
@@ -1797,7 +1721,7 @@ struct cs_engine {
     next_id = id;
     {
       const uint32_t nid = (uint32_t)next_id;  // the device path (cs_spawn_commit_dev) continues from here
-      HIP_OK(hipMemcpyAsync(&ctr->next_id, &nid, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+      HIP_OK(hipMemcpyAsync(&ctr.get()->next_id, &nid, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
       HIP_OK(hipStreamSynchronize(stream));
     }
     committed_spawns = (uint32_t)mine.size() - n_ghost_spawns;
@@ -1806,15 +1730,11 @@ struct cs_engine {
     if (mine.empty()) return 0;
     if (int rc = recount()) return rc;
     if (int rc = reserve((uint64_t)n_slots + mine.size())) return rc;
-    if (mine.size() > spawn_rec_cap) {
-      hipFree(spawn_rec_dev);
-      spawn_rec_cap = (uint32_t)mine.size() * 2u + 64u;
-      HIP_OK(hipMalloc(&spawn_rec_dev, (size_t)spawn_rec_cap * sizeof(SpawnRecord)));
-    }
-    HIP_OK(hipMemcpyAsync(spawn_rec_dev, mine.data(), mine.size() * sizeof(SpawnRecord),
+    if (mine.size() > spawn_rec_dev.count()) HIP_OK(spawn_rec_dev.alloc((uint32_t)mine.size() * 2u + 64u));
+    HIP_OK(hipMemcpyAsync(spawn_rec_dev.get(), mine.data(), mine.size() * sizeof(SpawnRecord),
                           hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_append_spawns, dim3(((uint32_t)mine.size() + 255) / 256), dim3(256), 0, stream,
-                       view(cur), (uint32_t)cap, spawn_rec_dev, (uint32_t)mine.size(), cell_count, ctr);
+                       view(cur), (uint32_t)cap, spawn_rec_dev.get(), (uint32_t)mine.size(), cell_count.get(), ctr.get());
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(stream));  // `mine` dies at return
     n_slots += (uint32_t)mine.size();
@@ -1830,20 +1750,20 @@ struct cs_engine {
   int spawn_probe_dev(double dt_seconds, int* flags_dev) {
     if (int rc = upload_sinks()) return rc;
     if (int rc = upload_groups()) return rc;
-    uint32_t* want = want_host + (size_t)want_ring * std::max<size_t>(sinks.size(), 1);
+    uint32_t* want = want_host.get() + (size_t)want_ring * std::max<size_t>(sinks.size(), 1);
     want_ring = (want_ring + 1) % kWantRing;
     pending_want = eval_generators(dt_seconds, want);
     if (want_on_device.size() != sinks.size() ||
         std::memcmp(want_on_device.data(), want, sinks.size() * sizeof(uint32_t)) != 0) {
-      HIP_OK(hipMemcpyAsync(want_dev, want, sinks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+      HIP_OK(hipMemcpyAsync(want_dev.get(), want, sinks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
       want_on_device.assign(want, want + sinks.size());
     }
     occ_valid = false;  // ghosts arrived since the step kernel marked its own agents
     if (int rc = mark_occupancy()) return rc;
     const uint32_t ns = (uint32_t)sinks.size();
     if (ns)
-      hipLaunchKernelGGL(k_spawn_probe_dev, dim3((ns + 255u) / 256u), dim3(256), 0, stream, sinks_dev, want_dev, ns,
-                         src_occupied, flags_dev);
+      hipLaunchKernelGGL(k_spawn_probe_dev, dim3((ns + 255u) / 256u), dim3(256), 0, stream, sinks_dev.get(), want_dev.get(), ns,
+                         src_occupied.get(), flags_dev);
     HIP_OK(hipGetLastError());
     return 0;
   }
@@ -1863,10 +1783,10 @@ struct cs_engine {
     if (int rc = reserve((uint64_t)n_slots + mine)) return rc;
     const uint32_t nb = (ns + SPAWN_BLOCK - 1u) / SPAWN_BLOCK;
     prof_begin(CS_K_SPAWN);
-    hipLaunchKernelGGL(k_spawn_count_flags, dim3(nb), dim3(SPAWN_BLOCK), 0, stream, flags_dev, ns, ctr,
-                       spawn_scratch);
+    hipLaunchKernelGGL(k_spawn_count_flags, dim3(nb), dim3(SPAWN_BLOCK), 0, stream, flags_dev, ns, ctr.get(),
+                       spawn_scratch.get());
     hipLaunchKernelGGL(k_spawn_commit_dev, dim3(nb), dim3(SPAWN_BLOCK), 0, stream, view(cur), (uint32_t)cap,
-                       sinks_dev, flags_dev, ns, cell_count, ctr, spawn_scratch);
+                       sinks_dev.get(), flags_dev, ns, cell_count.get(), ctr.get(), spawn_scratch.get());
     prof_end();
     HIP_OK(hipGetLastError());
     n_slots += mine;  // upper bound; kernels stop at the device-side count
@@ -1914,7 +1834,7 @@ struct cs_engine {
         ((has_sinks && !tile && async_steps + 1 < kWantRing) ||
          (tile && (!has_sinks || spawn_on_device) && async_steps + 1 < kTileAsync));
     if (has_sinks && !tile) {
-      uint32_t* want = want_host + (size_t)want_ring * std::max<size_t>(sinks.size(), 1);
+      uint32_t* want = want_host.get() + (size_t)want_ring * std::max<size_t>(sinks.size(), 1);
       want_ring = (want_ring + 1) % kWantRing;  // a slot is reused only after a host sync
       n_want = eval_generators(dt_seconds, want);
       if (n_want) {
@@ -1925,7 +1845,7 @@ struct cs_engine {
         // generators that ask for the same sinks every step (MonotonicCrowd) need no new upload
         if (want_on_device.size() != sinks.size() ||
             std::memcmp(want_on_device.data(), want, sinks.size() * sizeof(uint32_t)) != 0) {
-          HIP_OK(hipMemcpyAsync(want_dev, want, sinks.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+          HIP_OK(hipMemcpyAsync(want_dev.get(), want, sinks.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                                 stream));
           want_on_device.assign(want, want + sinks.size());
         }
@@ -1936,11 +1856,11 @@ struct cs_engine {
         prof_begin(CS_K_SPAWN);
         {
           const uint32_t nb = ((uint32_t)sinks.size() + SPAWN_BLOCK - 1u) / SPAWN_BLOCK;
-          hipLaunchKernelGGL(k_spawn_count, dim3(nb), dim3(SPAWN_BLOCK), 0, stream, sinks_dev, want_dev,
-                             (uint32_t)sinks.size(), src_occupied, ctr, spawn_scratch);
+          hipLaunchKernelGGL(k_spawn_count, dim3(nb), dim3(SPAWN_BLOCK), 0, stream, sinks_dev.get(), want_dev.get(),
+                             (uint32_t)sinks.size(), src_occupied.get(), ctr.get(), spawn_scratch.get());
           hipLaunchKernelGGL(k_spawn_apply, dim3(nb), dim3(SPAWN_BLOCK), 0, stream, view(cur), n_slots,
-                             (uint32_t)cap, sinks_dev, want_dev, (uint32_t)sinks.size(), n_want, src_occupied,
-                             cell_count, spawned_slots_dev, ctr, spawn_scratch);
+                             (uint32_t)cap, sinks_dev.get(), want_dev.get(), (uint32_t)sinks.size(), n_want, src_occupied.get(),
+                             cell_count.get(), spawned_slots_dev.get(), ctr.get(), spawn_scratch.get());
         }
         prof_end();
         HIP_OK(hipGetLastError());
@@ -1959,12 +1879,12 @@ struct cs_engine {
     }
 
     if (has_sinks && !spawn_ran && !(tile && spawn_on_device))  // n_spawned (n_halo_overflow is sticky)
-      HIP_OK(hipMemsetAsync(&ctr->n_spawned, 0, sizeof(uint32_t), stream));
+      HIP_OK(hipMemsetAsync(&ctr.get()->n_spawned, 0, sizeof(uint32_t), stream));
 
     // ---- index for this step (location_hash_2d.rs:126-149) ----
     const bool rebuilt = !sorted;
     if (!rebuilt)  // no re-sort this step: the scan is what normally zeroes the step counters
-      HIP_OK(hipMemsetAsync(&ctr->n_destroyed, 0, 6 * sizeof(uint32_t), stream));
+      HIP_OK(hipMemsetAsync(&ctr.get()->n_destroyed, 0, 6 * sizeof(uint32_t), stream));
     // the form of the neighbour kernel is known before the sort: LDS-tiled strips when the crowd
     // is large enough to fill them; its band windows are then built in the scatter launch
     const uint64_t n_rows = ncells / std::max<uint64_t>(nx, 1);
@@ -2025,7 +1945,7 @@ struct cs_engine {
       key.org_x = gdev.org_x; key.org_y = gdev.org_y;
       key.h = (uint32_t)h; key.desc_cap = blk_desc_cap; key.rows = tile_rows; key.target = band_target;
       key.stage_cap = stage_cap; key.split = split_margin();
-      key.desc = blk_desc < blk_desc_back ? blk_desc : blk_desc_back;  // (the pair; the two swap every step)
+      key.desc = blk_desc.get() < blk_desc_back.get() ? blk_desc.get() : blk_desc_back.get();  // (the pair; the two swap every step)
       keep_now = windows_valid && key == windows_key && n_slots != 0u;
       if (keep_now) n_steps_on_kept_windows += 1;
       windows_key = key;
@@ -2052,7 +1972,7 @@ struct cs_engine {
 
     // ---- Phases B + C: per-agent update and commit (lib.rs:259-359) ----
     if (has_sinks && !spawn_ran)
-      HIP_OK(hipMemsetAsync(src_occupied, 0, std::max<size_t>(sinks.size(), 1) * sizeof(uint32_t), stream));
+      HIP_OK(hipMemsetAsync(src_occupied.get(), 0, std::max<size_t>(sinks.size(), 1) * sizeof(uint32_t), stream));
     // cell_count is all zero here: the scan clears it while reading (k_scan_apply)
     if (tile && n_slots && !bands_built)  // ghosts get no thread: their output slots must read "dead"
       HIP_OK(hipMemsetAsync(buf[cur ^ 1].cell, 0xFF, (size_t)n_slots * sizeof(uint32_t), stream));  // (else the scatter did)
@@ -2065,54 +1985,54 @@ struct cs_engine {
     P.halo_late_check = 0;
     P.peek_seq = 0;
     if (tile) {
-      if (!peek_host) {
-        HIP_OK(hipHostMalloc(&peek_host, 3 * sizeof(unsigned long long)));
-        peek_host[0] = peek_host[1] = peek_host[2] = 0ull;
+      if (!peek_host.get()) {
+        HIP_OK(peek_host.alloc(3));
+        peek_host.get()[0] = peek_host.get()[1] = peek_host.get()[2] = 0ull;
       }
       P.peek_seq = peek_next();
     }
     EpilogueCtx E;
     memset(&E, 0, sizeof(E));  // (compared bytewise below)
     E.out = view(cur ^ 1);
-    E.cell_count = cell_count;
-    E.ctr = ctr;
-    E.groups = groups_dev;
-    E.sinks = sinks_dev;
-    E.waypoints = waypoints_dev;
+    E.cell_count = cell_count.get();
+    E.ctr = ctr.get();
+    E.groups = groups_dev.get();
+    E.sinks = sinks_dev.get();
+    E.waypoints = waypoints_dev.get();
     E.grid_off_x = grid.offset_x;
     E.grid_off_y = grid.offset_y;
     E.cell_size = grid.cell_size;
-    E.destroyed = destroyed;
+    E.destroyed = destroyed.get();
     E.destroyed_cap = destroyed_cap;
-    E.wp_events = wp_events;
+    E.wp_events = wp_events.get();
     E.wp_events_cap = wp_events_cap;
-    E.src_cell_start = src_cell_start;
-    E.src_sorted = src_sorted;
-    E.src_occupied = src_occupied;
-    E.route_desc = route_desc_dev;
-    E.route_xy = route_xy_dev;
-    E.route_book = any_route_hlp ? route_book_dev : nullptr;
+    E.src_cell_start = src_cell_start.get();
+    E.src_sorted = src_sorted.get();
+    E.src_occupied = src_occupied.get();
+    E.route_desc = route_desc_dev.get();
+    E.route_xy = route_xy_dev.get();
+    E.route_book = any_route_hlp ? route_book_dev.get() : nullptr;
     E.route_book_mask = route_book_size ? route_book_size - 1u : 0u;
-    E.hlp_route_scale = hlp_scale_dev;
-    if (any_callback_lp && n_slots && !lp_vel) {
-      HIP_OK(hipMalloc(&lp_vel, cap * sizeof(float2)));
-      HIP_OK(hipMemsetAsync(lp_vel, 0, cap * sizeof(float2), stream));
+    E.hlp_route_scale = hlp_scale_dev.get();
+    if (any_callback_lp && n_slots && !lp_vel.get()) {
+      HIP_OK(lp_vel.alloc(cap));
+      HIP_OK(hipMemsetAsync(lp_vel.get(), 0, cap * sizeof(float2), stream));
     }
-    E.lp_vel = any_callback_lp ? lp_vel : nullptr;
-    E.peek = tile ? peek_host : nullptr;
+    E.lp_vel = any_callback_lp ? lp_vel.get() : nullptr;
+    E.peek = tile ? peek_host.get() : nullptr;
     // (keep_now: this step runs on the windows of the step before and cuts its own, for the next one, in the
     // neighbour kernel's launch.  Also where no sort was due, a query or a read between two steps having sorted already:
     // that sort's scan zeroed the owned count with nobody behind it to count again, which the builders do as they go;
     // the scan of a step's own sort clears the other array's window count, here it is cleared by hand)
     const uint32_t builders = (keep_now && n_slots) ? n_bands : 0u;
-    if (builders && !rebuilt) HIP_OK(hipMemsetAsync(n_blocks_back, 0, 2 * sizeof(uint32_t), stream));
+    if (builders && !rebuilt) HIP_OK(hipMemsetAsync(n_blocks_back.get(), 0, 2 * sizeof(uint32_t), stream));
     if (builders) {
-      const bool front_low = blk_desc < blk_desc_back;  // (address order: the same context every step)
-      E.build_desc[0] = front_low ? blk_desc : blk_desc_back;
-      E.build_desc[1] = front_low ? blk_desc_back : blk_desc;
-      E.build_n_blocks[0] = front_low ? n_blocks_dev : n_blocks_back;
-      E.build_n_blocks[1] = front_low ? n_blocks_back : n_blocks_dev;
-      E.build_prefix = band_prefix;
+      const bool front_low = blk_desc.get() < blk_desc_back.get();  // (address order: the same context every step)
+      E.build_desc[0] = front_low ? blk_desc.get() : blk_desc_back.get();
+      E.build_desc[1] = front_low ? blk_desc_back.get() : blk_desc.get();
+      E.build_n_blocks[0] = front_low ? n_blocks_dev.get() : n_blocks_back.get();
+      E.build_n_blocks[1] = front_low ? n_blocks_back.get() : n_blocks_dev.get();
+      E.build_prefix = band_prefix.get();
       E.build_first = 0u;
       E.build_bands = builders;
       E.build_rows = tile_rows;
@@ -2143,18 +2063,18 @@ struct cs_engine {
     // a host synchronisation.  (The kernel's other arguments stayed by-value: moving the input
     // arrays and the tile configuration here as well cost 5 %, they are read in the hot loops.)
     const int epi_slot = cur ^ 1;
-    if (!epi_dev) {
-      HIP_OK(hipMalloc(&epi_dev, 2 * sizeof(EpilogueCtx)));
+    if (!epi_dev.get()) {
+      HIP_OK(epi_dev.alloc(2));
       epi_host = new EpilogueCtx[2];
       epi_valid[0] = epi_valid[1] = false;
     }
     if (!epi_valid[epi_slot] || memcmp(&epi_host[epi_slot], &E, sizeof(E)) != 0) {
       memcpy(&epi_host[epi_slot], &E, sizeof(E));
-      hipLaunchKernelGGL(k_store_ctx, dim3(1), dim3(64), 0, stream, E, &epi_dev[epi_slot]);
+      hipLaunchKernelGGL(k_store_ctx, dim3(1), dim3(64), 0, stream, E, &epi_dev.get()[epi_slot]);
       HIP_OK(hipGetLastError());
       epi_valid[epi_slot] = true;
     }
-    const EpilogueCtx* Ep = &epi_dev[epi_slot];
+    const EpilogueCtx* Ep = &epi_dev.get()[epi_slot];
     // ---- LocalPlanner callbacks (slow path, local_planner.rs:7-18 at lib.rs:276-291) ----
     if (any_callback_lp && n_slots)
       if (int rc = lp_callbacks_eval(this, P, Ep)) return rc;
@@ -2214,15 +2134,15 @@ struct cs_engine {
       if (builders) lds = std::max<size_t>(lds, BAND_SCRATCH_BYTES);  // (the builder workgroups' arrays live there)
       uint32_t grid_blocks;
       if (rb <= 1) {
-        hipLaunchKernelGGL(k_build_blocks, dim3(1), dim3(1024), 0, stream, gdev, cell_start, blk_desc,
-                           blk_desc_cap, n_blocks_dev, ctr);
+        hipLaunchKernelGGL(k_build_blocks, dim3(1), dim3(1024), 0, stream, gdev, cell_start.get(), blk_desc.get(),
+                           blk_desc_cap, n_blocks_dev.get(), ctr.get());
         grid_blocks = (n_slots + TILE_THREADS - 1u) / TILE_THREADS + (uint32_t)std::min<uint64_t>(n_rows, n_slots);
       } else {
         if (!bands_built && !keep_now) {  // (kept windows tile the bands whether or not a sort was due)
-          if (!rebuilt) HIP_OK(hipMemsetAsync(n_blocks_dev, 0, 2 * sizeof(uint32_t), stream));  // else the scan did
-          hipLaunchKernelGGL(k_build_bands, dim3(n_bands), dim3(256), 0, stream, gdev, cell_start, rb,
+          if (!rebuilt) HIP_OK(hipMemsetAsync(n_blocks_dev.get(), 0, 2 * sizeof(uint32_t), stream));  // else the scan did
+          hipLaunchKernelGGL(k_build_bands, dim3(n_bands), dim3(256), 0, stream, gdev, cell_start.get(), rb,
                              band_target, (uint32_t)h, build_stage_cap, tile_max_cols((uint32_t)h), split_margin(), want_keep ? 1u : 0u,
-                             band_prefix, blk_desc, blk_desc_cap, n_blocks_dev, ctr);
+                             band_prefix.get(), blk_desc.get(), blk_desc_cap, n_blocks_dev.get(), ctr.get());
           cover_built_late = want_keep;
         }
         // two consecutive greedy windows of a band hold more than tile_target agents together
@@ -2246,18 +2166,16 @@ struct cs_engine {
       {
         // (a split step's two launches may run side by side: each has its own spill area)
         const uint64_t words = (uint64_t)grid_blocks * cfg.spill_rows * TILE_THREADS * (split ? 2u : 1u);
-        if (words > tile_spill_words) {
+        if (words > tile_spill.count()) {
           HIP_OK(hipStreamSynchronize(stream));
-          hipFree(tile_spill);
-          tile_spill_words = words + words / 4;
-          HIP_OK(hipMalloc(&tile_spill, tile_spill_words * sizeof(uint32_t)));
+          HIP_OK(tile_spill.alloc(words + words / 4));
         }
       }
-      cfg.spill = tile_spill;
+      cfg.spill = tile_spill.get();
       cfg.part = 0;
       cfg.desc_cap = blk_desc_cap;
       cfg.split = split ? 1u : 0u;
-      cfg.build_sel = (builders && blk_desc < blk_desc_back) ? 1u : 0u;  // (the back array's place in the context)
+      cfg.build_sel = (builders && blk_desc.get() < blk_desc_back.get()) ? 1u : 0u;  // (the back array's place in the context)
       // (crowds whose agents all run the waypoint test keep the context in registers: k_step_tiled)
       // (CS_DEBUG_CTX_BY_VALUE=1, measurement only: a plain crowd through the instantiation with 146 spilled scalars,
       //  profiles/K4_LEVERS.md round 5)
@@ -2269,20 +2187,20 @@ struct cs_engine {
         const dim3 grid(grid_blocks + builders), block(TILE_THREADS);
         const EpilogueCore& Ec = static_cast<const EpilogueCore&>(E);
         if (ctx_by_value && builders)
-          hipLaunchKernelGGL((k_step_tiled<true, true, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
+          hipLaunchKernelGGL((k_step_tiled<true, true, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start.get(), pref.get(), blk_desc.get(), n_blocks_dev.get(), c);
         else if (ctx_by_value)
-          hipLaunchKernelGGL((k_step_tiled<true, false, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
+          hipLaunchKernelGGL((k_step_tiled<true, false, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start.get(), pref.get(), blk_desc.get(), n_blocks_dev.get(), c);
         else if (builders)
-          hipLaunchKernelGGL((k_step_tiled<false, true, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
+          hipLaunchKernelGGL((k_step_tiled<false, true, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start.get(), pref.get(), blk_desc.get(), n_blocks_dev.get(), c);
         else
-          hipLaunchKernelGGL((k_step_tiled<false, false, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c);
+          hipLaunchKernelGGL((k_step_tiled<false, false, false, XF>), grid, block, lds, s, Pl, view(cur), Ep, Ec, cell_start.get(), pref.get(), blk_desc.get(), n_blocks_dev.get(), c);
       };
       auto launch_tiled = [&](hipStream_t s, const StepParams& Pl, const TileCfg& c) {
         if (x_float) launch_tiled_as(std::true_type{}, s, Pl, c);
         else launch_tiled_as(std::false_type{}, s, Pl, c);
       };
       if (check_windows && n_slots && rb > 1 && !split)
-        if (int rc = check_window_list(blk_desc, n_blocks_dev, rb, n_bands, tile_max_cols((uint32_t)h), want_keep, grid_blocks)) return rc;
+        if (int rc = check_window_list(blk_desc.get(), n_blocks_dev.get(), rb, n_bands, tile_max_cols((uint32_t)h), want_keep, grid_blocks)) return rc;
       if (n_slots && P.peek_seq) flight_launched(P.peek_seq);
       prof_begin(CS_K_NEIGHBOUR_FORCE);
       early_pending = false;
@@ -2302,13 +2220,13 @@ struct cs_engine {
           const dim3 grid(grid_blocks), block(TILE_THREADS);  // (no builder workgroups: kept windows and a split exclude each other)
           const EpilogueCore& Ec = static_cast<const EpilogueCore&>(E);
           if (ctx_by_value && x_float)
-            hipLaunchKernelGGL((k_step_tiled<true, false, true, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c2);
+            hipLaunchKernelGGL((k_step_tiled<true, false, true, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start.get(), pref.get(), blk_desc.get(), n_blocks_dev.get(), c2);
           else if (ctx_by_value)
-            hipLaunchKernelGGL((k_step_tiled<true, false, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c2);
+            hipLaunchKernelGGL((k_step_tiled<true, false, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start.get(), pref.get(), blk_desc.get(), n_blocks_dev.get(), c2);
           else if (x_float)
-            hipLaunchKernelGGL((k_step_tiled<false, false, true, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c2);
+            hipLaunchKernelGGL((k_step_tiled<false, false, true, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start.get(), pref.get(), blk_desc.get(), n_blocks_dev.get(), c2);
           else
-            hipLaunchKernelGGL((k_step_tiled<false, false, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start, pref, blk_desc, n_blocks_dev, c2);
+            hipLaunchKernelGGL((k_step_tiled<false, false, true>), grid, block, lds, stream, Pc, view(cur), Ep, Ec, cell_start.get(), pref.get(), blk_desc.get(), n_blocks_dev.get(), c2);
         }
         border_on_aux = true;
         early_pending = true;
@@ -2319,7 +2237,7 @@ struct cs_engine {
         // stream, which the caller then hands the exchange to.
         TileCfg cfg_b = cfg;
         cfg_b.part = 1;
-        cfg_b.spill = tile_spill + (uint64_t)grid_blocks * cfg.spill_rows * TILE_THREADS;
+        cfg_b.spill = tile_spill.get() + (uint64_t)grid_blocks * cfg.spill_rows * TILE_THREADS;
         hipStream_t sb = stream;
         border_on_aux = false;
         if (overlap_ready && (!need_host || fire_and_forget)) {
@@ -2346,19 +2264,19 @@ struct cs_engine {
       prof_end();
     } else {
       if (tile)  // owned count + slot count of the step output
-        hipLaunchKernelGGL(k_build_blocks, dim3(1), dim3(1024), 0, stream, gdev, cell_start, blk_desc,
-                           blk_desc_cap, n_blocks_dev, ctr);
+        hipLaunchKernelGGL(k_build_blocks, dim3(1), dim3(1024), 0, stream, gdev, cell_start.get(), blk_desc.get(),
+                           blk_desc_cap, n_blocks_dev.get(), ctr.get());
       if (n_slots && P.peek_seq) flight_launched(P.peek_seq);
       prof_begin(CS_K_NEIGHBOUR_FORCE);
       if (n_slots)
         hipLaunchKernelGGL(k_step_gather, dim3((n_slots + 255) / 256), dim3(256), 0, stream, P, view(cur),
-                           Ep, cell_start, pref);
+                           Ep, cell_start.get(), pref.get());
       prof_end();
     }
     HIP_OK(hipGetLastError());
-    last_windows_count = (tiled && n_slots) ? n_blocks_dev : nullptr;  // (CS_STAT_WINDOWS_LISTED; before the swap below)
+    last_windows_count = (tiled && n_slots) ? n_blocks_dev.get() : nullptr;  // (CS_STAT_WINDOWS_LISTED; before the swap below)
     if (builders && check_windows)
-      if (int rc = check_window_list(blk_desc_back, n_blocks_back, tile_rows, n_bands, tile_max_cols((uint32_t)h), true, 0xFFFFFFFFu)) return rc;
+      if (int rc = check_window_list(blk_desc_back.get(), n_blocks_back.get(), tile_rows, n_bands, tile_max_cols((uint32_t)h), true, 0xFFFFFFFFu)) return rc;
     if (builders) {  // the launch above has cut the next step's windows into the other array
       std::swap(blk_desc, blk_desc_back);
       std::swap(n_blocks_dev, n_blocks_back);
@@ -2408,8 +2326,8 @@ struct cs_engine {
     if (c.n_out_of_bounds || limbo_fail) {
       // "Index out of bounds" (location_hash_2d.rs:61-63 via lib.rs:299-302): nothing is
       // committed; the pre-step state (including this step's spawns) stays current.
-      HIP_OK(hipMemsetAsync(&ctr->n_out_of_bounds, 0, sizeof(uint32_t), stream));
-      HIP_OK(hipMemsetAsync(cell_count, 0, (ncells + 1) * sizeof(uint32_t), stream));  // partial histogram
+      HIP_OK(hipMemsetAsync(&ctr.get()->n_out_of_bounds, 0, sizeof(uint32_t), stream));
+      HIP_OK(hipMemsetAsync(cell_count.get(), 0, (ncells + 1) * sizeof(uint32_t), stream));  // partial histogram
       hist_valid = false;
       occ_valid = false;
       halo_invalidate();  // (records of a step that did not happen)
@@ -2471,7 +2389,7 @@ struct cs_engine {
     if (!n_spawned) return 0;
     if (!record_events && !any_callback_hlp) return 0;  // nobody listens: nothing to read back
     std::vector<uint32_t> slots(n_spawned);
-    HIP_OK(hipMemcpy(slots.data(), spawned_slots_dev, n_spawned * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(slots.data(), spawned_slots_dev.get(), n_spawned * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (uint32_t k = 0; k < n_spawned; ++k) {
       const HostSink& h = sinks[slots[k]];
       cs_event ev;
@@ -2508,7 +2426,7 @@ struct cs_engine {
     if (c.n_wp_events && (any_callback_hlp || any_route_hlp)) {
       uint32_t m = std::min(c.n_wp_events, wp_events_cap);
       std::vector<WpEvent> w(m);
-      HIP_OK(hipMemcpy(w.data(), wp_events, m * sizeof(WpEvent), hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(w.data(), wp_events.get(), m * sizeof(WpEvent), hipMemcpyDeviceToHost));
       std::sort(w.begin(), w.end(), [](const WpEvent& a, const WpEvent& b) { return a.id < b.id; });
       for (const WpEvent& ev : w) {  // ascending id = the canonical visiting order
         const HostGroup& g = groups[ev.group];
@@ -2533,7 +2451,7 @@ struct cs_engine {
     if (c.n_destroyed && (record_events || any_callback_hlp)) {
       uint32_t m = std::min(c.n_destroyed, destroyed_cap);
       std::vector<uint2> d(m);
-      HIP_OK(hipMemcpy(d.data(), destroyed, m * sizeof(uint2), hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(d.data(), destroyed.get(), m * sizeof(uint2), hipMemcpyDeviceToHost));
       std::sort(d.begin(), d.end(), [](const uint2& a, const uint2& b) { return a.x < b.x; });
       for (auto& it : d) {
         const HostGroup& g = groups[meta_group(gdev, it.y)];
@@ -2575,7 +2493,7 @@ struct cs_engine {
       prof_begin(CS_K_HALO);
       hipLaunchKernelGGL(k_halo_pack, dim3((n_slots + 255) / 256), dim3(256), 0, stream, gdev, view(cur),
                          n_slots, axis, 2u * halo_cells, lo.send, hi.send,
-                         std::max(lo.cap, hi.cap), ctr, other_lo.send, other_hi.send);
+                         std::max(lo.cap, hi.cap), ctr.get(), other_lo.send, other_hi.send);
       prof_end();
       halo_counts_clean[axis ^ 1u] = true;
     }
@@ -2593,7 +2511,7 @@ struct cs_engine {
     const uint32_t blocks = (dcap + 255u) / 256u;
     prof_begin(CS_K_HALO);
     hipLaunchKernelGGL(k_halo_unpack, dim3(2u * blocks), dim3(256), 0, stream, gdev, view(cur), (uint32_t)cap,
-                       a.recv, b.recv, dcap, blocks, cell_count, ctr);
+                       a.recv, b.recv, dcap, blocks, cell_count.get(), ctr.get());
     prof_end();
     n_slots += add;  // upper bound; kernels stop at the device-side count
     slots_added += add;
@@ -2633,7 +2551,7 @@ struct cs_engine {
     if (any && n_slots) {
       prof_begin(CS_K_HALO_PACK);
       hipLaunchKernelGGL(k_halo_pack_all, dim3((n_slots + 255) / 256), dim3(256), 0, stream, gdev, view(cur),
-                         n_slots, 2u * halo_cells, send, ctr);
+                         n_slots, 2u * halo_cells, send, ctr.get());
       prof_end();
     }
     HIP_OK(hipGetLastError());
@@ -2660,7 +2578,7 @@ struct cs_engine {
     const uint32_t blocks = (hcap + 255u) / 256u;
     prof_begin(CS_K_HALO_UNPACK);
     hipLaunchKernelGGL(k_halo_unpack_all, dim3(8u * blocks), dim3(256), 0, stream, gdev, view(cur), (uint32_t)cap,
-                       recv, send, blocks, cell_count, ctr, mesh_step_tag);
+                       recv, send, blocks, cell_count.get(), ctr.get(), mesh_step_tag);
     prof_end();
     halo_all_clean = true;  // the kernel reset the send counts
     n_slots += add;  // upper bound; kernels stop at the device-side count
@@ -2709,35 +2627,33 @@ struct cs_engine {
     gdev.own_y1 = oy1;
     gdev.org_x = org_x;
     gdev.org_y = org_y;
-    hipFree(cell_count); hipFree(cell_start); hipFree(block_totals); hipFree(band_prefix); hipFree(src_cell_start);
-    cell_count = cell_start = block_totals = band_prefix = src_cell_start = nullptr;
+    cell_count.release(); cell_start.release(); block_totals.release(); band_prefix.release(); src_cell_start.release();
     n_scan_blocks = (uint32_t)std::max<uint64_t>(1, (ncells + SCAN_TILE - 1) / SCAN_TILE);
-    HIP_OK(hipMalloc(&cell_count, (ncells + 1) * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&cell_start, (ncells + 1) * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&block_totals, n_scan_blocks * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&band_prefix, (ncells + 1) * sizeof(uint32_t)));
-    HIP_OK(hipMemset(cell_count, 0, (ncells + 1) * sizeof(uint32_t)));
-    HIP_OK(hipMemset(cell_start, 0, (ncells + 1) * sizeof(uint32_t)));
+    HIP_OK(cell_count.alloc(ncells + 1));
+    HIP_OK(cell_start.alloc(ncells + 1));
+    HIP_OK(block_totals.alloc(n_scan_blocks));
+    HIP_OK(band_prefix.alloc(ncells + 1));
+    HIP_OK(hipMemset(cell_count.get(), 0, (ncells + 1) * sizeof(uint32_t)));
+    HIP_OK(hipMemset(cell_start.get(), 0, (ncells + 1) * sizeof(uint32_t)));
     return 0;
   }
 
   // ---- re-cutting a running mesh: export everything owned, take a new rectangle, import ----
   int tile_histogram(uint64_t* rows, uint64_t* cols) {
     if (int rc = refresh_counts()) return rc;
-    uint32_t *d_rows = nullptr, *d_cols = nullptr;
-    HIP_OK(hipMalloc(&d_rows, gny * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&d_cols, gnx * sizeof(uint32_t)));
+    DevBuf<uint32_t> rows_mem, cols_mem;
+    HIP_OK(rows_mem.alloc(gny));
+    HIP_OK(cols_mem.alloc(gnx));
+    uint32_t *d_rows = rows_mem.get(), *d_cols = cols_mem.get();
     HIP_OK(hipMemsetAsync(d_rows, 0, gny * sizeof(uint32_t), stream));
     HIP_OK(hipMemsetAsync(d_cols, 0, gnx * sizeof(uint32_t), stream));
     if (n_slots)
-      hipLaunchKernelGGL(k_tile_histogram, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, gdev, view(cur), n_slots, ctr,
+      hipLaunchKernelGGL(k_tile_histogram, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, gdev, view(cur), n_slots, ctr.get(),
                          (tile && ghosts_present) ? 1u : 0u, d_rows, d_cols);
     std::vector<uint32_t> hr(gny), hc(gnx);
     HIP_OK(hipMemcpyAsync(hr.data(), d_rows, gny * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipMemcpyAsync(hc.data(), d_cols, gnx * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    hipFree(d_rows);
-    hipFree(d_cols);
     for (uint64_t k = 0; k < gny; ++k) rows[k] += hr[k];
     for (uint64_t k = 0; k < gnx; ++k) cols[k] += hc[k];
     return 0;
@@ -2745,24 +2661,24 @@ struct cs_engine {
   // returns the number of owned agents; writes min(that, cap) records
   long long tile_export(HaloRecord* out, size_t cap_records) {
     if (refresh_counts() != 0) return -1;
-    HaloRecord* d_out = nullptr;
-    uint32_t* d_count = nullptr;
+    DevBuf<HaloRecord> out_mem;
+    DevBuf<uint32_t> count_mem;
     const uint32_t cap_dev = (uint32_t)std::min<size_t>(std::max<size_t>(cap_records, 1), n_slots + 1u);
-    if (hipMalloc(&d_out, (size_t)cap_dev * sizeof(HaloRecord)) != hipSuccess || hipMalloc(&d_count, sizeof(uint32_t)) != hipSuccess) {
+    if (out_mem.alloc(cap_dev) != hipSuccess || count_mem.alloc(1) != hipSuccess) {
       error = "HIP error while exporting a tile";
       return -1;
     }
+    HaloRecord* d_out = out_mem.get();
+    uint32_t* d_count = count_mem.get();
     uint32_t count = 0;
     bool ok = hipMemsetAsync(d_count, 0, sizeof(uint32_t), stream) == hipSuccess;
     if (n_slots)
-      hipLaunchKernelGGL(k_tile_export, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, gdev, view(cur), n_slots, ctr,
+      hipLaunchKernelGGL(k_tile_export, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, gdev, view(cur), n_slots, ctr.get(),
                          (tile && ghosts_present) ? 1u : 0u, d_out, cap_dev, d_count);
     ok = ok && hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, stream) == hipSuccess &&
          hipStreamSynchronize(stream) == hipSuccess;
     const size_t m = std::min<size_t>(std::min<size_t>(count, cap_dev), cap_records);
     if (ok && m && out) ok = hipMemcpy(out, d_out, m * sizeof(HaloRecord), hipMemcpyDeviceToHost) == hipSuccess;
-    hipFree(d_out);
-    hipFree(d_count);
     if (!ok) {
       error = "HIP error while exporting a tile";
       return -1;
@@ -2791,9 +2707,9 @@ struct cs_engine {
     spawn_committed = false;
     {
       Counters c;
-      HIP_OK(hipMemcpy(&c, ctr, sizeof c, hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(&c, ctr.get(), sizeof c, hipMemcpyDeviceToHost));
       c.n_alive = c.n_owned = c.n_pending = c.n_spawned = c.n_destroyed = 0;
-      HIP_OK(hipMemcpy(ctr, &c, sizeof c, hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(ctr.get(), &c, sizeof c, hipMemcpyHostToDevice));
     }
     for (auto& h : halo) h = HaloDir{};  // the caller sets buffers for the new neighbours' edges
     halo_all_clean = false;
@@ -2817,19 +2733,19 @@ struct cs_engine {
     if (int rc = upload_groups()) return rc;
     if (int rc = recount()) return rc;
     if (int rc = reserve((uint64_t)n_slots + n)) return rc;
-    HaloRecord* d_rec = nullptr;
-    uint32_t* d_kept = nullptr;
-    HIP_OK(hipMalloc(&d_rec, n * sizeof(HaloRecord)));
-    HIP_OK(hipMalloc(&d_kept, sizeof(uint32_t)));
+    DevBuf<HaloRecord> rec_mem;
+    DevBuf<uint32_t> kept_mem;
+    HIP_OK(rec_mem.alloc(n));
+    HIP_OK(kept_mem.alloc(1));
+    HaloRecord* d_rec = rec_mem.get();
+    uint32_t* d_kept = kept_mem.get();
     HIP_OK(hipMemcpy(d_rec, rec, n * sizeof(HaloRecord), hipMemcpyHostToDevice));
     HIP_OK(hipMemsetAsync(d_kept, 0, sizeof(uint32_t), stream));
     hipLaunchKernelGGL(k_tile_import, dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, stream, gdev, view(cur), (uint32_t)cap,
-                       d_rec, (uint32_t)n, cell_count, ctr, d_kept);
+                       d_rec, (uint32_t)n, cell_count.get(), ctr.get(), d_kept);
     uint32_t kept = 0;
     HIP_OK(hipMemcpyAsync(&kept, d_kept, sizeof kept, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    hipFree(d_rec);
-    hipFree(d_kept);
     n_slots += kept;
     slots_added_total += kept;
     n_alive_host += kept;
@@ -2844,18 +2760,18 @@ struct cs_engine {
     uint64_t b = 0;
     b += 2ull * cap * (2 * sizeof(float2) + 5 * sizeof(uint32_t));                    // the two agent buffers
     b += cap * sizeof(float2) + (uint64_t)destroyed_cap * sizeof(uint2) + (uint64_t)wp_events_cap * sizeof(WpEvent);
-    b += (uint64_t)blk_desc_cap * sizeof(BlockDesc) + tile_spill_words * sizeof(uint32_t);
+    b += (uint64_t)blk_desc_cap * sizeof(BlockDesc) + tile_spill.bytes();
     b += 4ull * (ncells + 1) * sizeof(uint32_t) + (uint64_t)n_scan_blocks * sizeof(uint32_t);  // cell tables
-    b += sinks.size() * (sizeof(SinkDev) + 5 * sizeof(uint32_t)) + (uint64_t)spawn_rec_cap * sizeof(SpawnRecord);
-    b += route_desc_cap * sizeof(uint2) + route_xy_cap * sizeof(double) + (uint64_t)route_book_size * sizeof(RouteBookEntry) +
-         hlp_scale_cap * sizeof(double) + route_pending_cap * sizeof(uint2);
+    b += sinks.size() * (sizeof(SinkDev) + 5 * sizeof(uint32_t)) + spawn_rec_dev.bytes();
+    b += route_desc_dev.bytes() + route_xy_dev.bytes() + (uint64_t)route_book_size * sizeof(RouteBookEntry) +
+         hlp_scale_dev.bytes() + route_pending_dev.bytes();
     for (const Snapshot& sn : snap) b += sn.cap * sizeof(cs_snapshot_record);
-    b += write_scratch_bytes;  // the batches of the by-id calls (write, read, remove) and the selections' lists
-    b += sel_groups_cap * sizeof(SelGroupDev);
-    b += field_scratch_bytes;  // the raster of the last cs_agent_field (cs_field.hip.inc)
+    b += write_scratch.bytes();  // the batches of the by-id calls (write, read, remove) and the selections' lists
+    b += sel_groups_dev.bytes();
+    b += field_scratch.bytes();  // the raster of the last cs_agent_field (cs_field.hip.inc)
     b += hlp_field_bytes();    // the field planners' samples and their table (cs_hlp_field.hip.inc)
-    b += flow_scratch_bytes;   // the rasters of the last cs_flow_field_solve (cs_flow_solve.hip.inc)
-    b += pairs_scratch_bytes;  // the kept part of the lists of the distance queries, at most 16 MiB (cs_near.hip.inc)
+    b += flow_scratch.bytes();  // the rasters of the last cs_flow_field_solve (cs_flow_solve.hip.inc)
+    b += pairs_scratch.bytes();  // the kept part of the lists of the distance queries, at most 16 MiB (cs_near.hip.inc)
     return b;
   }
 
@@ -2864,23 +2780,4 @@ struct cs_engine {
     if (sorted) return 0;
     return rebuild();
   }
-
-  void* write_scratch = nullptr;  // device scratch of the by-id calls: cs_write_agents, cs_read_agents_by_id, cs_remove_agents
-                                  // (grown as needed, never shrunk: cs_agent_write.hip.inc)
-  size_t write_scratch_bytes = 0;
-  // the selections' view of the planner groups (cs_select.hip.inc): refreshed inside a selection when a group was added
-  // since, with a flag of its own, so that a selection leaves groups_dirty and the step's tables alone
-  SelGroupDev* sel_groups_dev = nullptr;
-  size_t sel_groups_cap = 0;
-  bool sel_groups_dirty = true;
-  // the raster of cs_agent_field (cs_field.hip.inc): grown to the largest raster asked for, never shrunk
-  void* field_scratch = nullptr;
-  size_t field_scratch_bytes = 0;
-  // the rasters of cs_flow_field_solve (cs_flow_solve.hip.inc): grown to the largest solve asked for, never shrunk
-  void* flow_scratch = nullptr;
-  size_t flow_scratch_bytes = 0;
-  // the lists of cs_close_pairs, cs_agent_clusters and cs_agent_neighbours (PairsScratch, cs_near.hip.inc): kept while
-  // they need at most PAIRS_SCRATCH_KEEP bytes; a larger list is allocated for its call and freed before it returns
-  void* pairs_scratch = nullptr;
-  size_t pairs_scratch_bytes = 0;
 };

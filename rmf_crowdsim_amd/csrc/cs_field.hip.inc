@@ -180,19 +180,7 @@ size_t field_lds_limit() {
 }
 
 int field_scratch_reserve(cs_engine* e, size_t need) {
-  if (need <= e->field_scratch_bytes) return 0;
-  if (e->field_scratch) {
-    HIP_OK_E(e, hipStreamSynchronize(e->stream));
-    hipFree(e->field_scratch);
-  }
-  e->field_scratch = nullptr;
-  e->field_scratch_bytes = 0;
-  if (hipMalloc(&e->field_scratch, need) != hipSuccess) {
-    e->error = "agent_field: out of device memory for the raster";
-    return 90;
-  }
-  e->field_scratch_bytes = need;
-  return 0;
+  return scratch_reserve(e, e->field_scratch, need, "agent_field: out of device memory for the raster");
 }
 
 // K_field on one engine (after sel_begin): the raster of its (owned) slots in its scratch, zeroed and filled on the
@@ -201,7 +189,7 @@ int field_run(cs_engine* e, const cs_field_desc& d, const cs_selection& s, bool 
   const size_t bins = (size_t)d.nx * d.ny;
   const size_t b_cnt = sel_up(bins * sizeof(uint32_t)), b_sum = want_sums ? sel_up(bins * sizeof(double)) : 0u;
   if (int rc = field_scratch_reserve(e, 256u + b_cnt + 2u * b_sum)) return rc;
-  unsigned char* sc = static_cast<unsigned char*>(e->field_scratch);
+  unsigned char* sc = static_cast<unsigned char*>(e->field_scratch.get());
   out->box = reinterpret_cast<uint32_t*>(sc);
   out->cnt = reinterpret_cast<uint32_t*>(sc + 256u);
   out->svx = want_sums ? reinterpret_cast<double*>(sc + 256u + b_cnt) : nullptr;
@@ -219,7 +207,7 @@ int field_run(cs_engine* e, const cs_field_desc& d, const cs_selection& s, bool 
   const uint32_t load_vel = (want_sums || (s.terms & CS_SEL_SPEED)) ? 1u : 0u;
   auto kernel = in_lds ? k_field<true> : k_field<false>;
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(FIELD_BLOCK), in_lds ? lds : 0u, e->stream, e->gdev, e->buf[e->cur], n,
-                     e->ctr, e->tile ? 1u : 0u, (e->tile && e->ghosts_present) ? 1u : 0u, e->sel_groups_dev,
+                     e->ctr.get(), e->tile ? 1u : 0u, (e->tile && e->ghosts_present) ? 1u : 0u, e->sel_groups_dev.get(),
                      (uint32_t)e->groups.size(), e->grid.offset_x, e->grid.offset_y, e->grid.cell_size, d, s,
                      want_sums ? 1u : 0u, load_vel, out->cnt, out->svx, out->svy, want_box ? out->box : nullptr);
   HIP_OK_E(e, hipGetLastError());

@@ -274,20 +274,9 @@ int flow_planner(cs_engine* e, const cs_field_desc& d, uint32_t hlp, HostHlpFiel
 }
 
 int flow_scratch_reserve(cs_engine* e, size_t need) {
-  if (need <= e->flow_scratch_bytes) return 0;
-  if (e->flow_scratch) {
-    HIP_OK_E(e, hipStreamSynchronize(e->stream));
-    hipFree(e->flow_scratch);
-  }
-  e->flow_scratch = nullptr;
-  e->flow_scratch_bytes = 0;
-  if (hipMalloc(&e->flow_scratch, need) != hipSuccess) {
-    (void)hipGetLastError();
-    e->error = "flow_field_solve: out of device memory for the solve";
-    return 90;
-  }
-  e->flow_scratch_bytes = need;
-  return 0;
+  const int rc = scratch_reserve(e, e->flow_scratch, need, "flow_field_solve: out of device memory for the solve");
+  if (rc && !e->flow_scratch.get()) (void)hipGetLastError();  // (the failed allocation's)
+  return rc;
 }
 
 // The solve on one engine, after the checks.  counts_dev: the counts on this engine's device (field_run's), or
@@ -310,13 +299,13 @@ int flow_run(cs_engine* e, const cs_flow_desc& f, uint32_t* counts_dev, const ui
   const size_t b_act = sel_up((size_t)n_tiles * sizeof(uint32_t)), b_u8 = sel_up(bins);
   const size_t need = b_hdr + 2u * b_f64 + b_vec + b_slow + b_cnt + b_extra + 2u * b_act + (f.blocked ? 3u : 2u) * b_u8;
   if (int rc = flow_scratch_reserve(e, need)) return rc;
-  unsigned char* p = static_cast<unsigned char*>(e->flow_scratch);
+  unsigned char* p = static_cast<unsigned char*>(e->flow_scratch.get());
   uint32_t* hdr = reinterpret_cast<uint32_t*>(p);  // [0 .. FLOW_BATCH): the rounds' counters; byte 64: reached (u64)
   unsigned long long* reached_dev = reinterpret_cast<unsigned long long*>(p + 64u);
   p += b_hdr;
   double* dist = reinterpret_cast<double*>(p); p += b_f64;
   double* sv = reinterpret_cast<double*>(p); p += b_f64;
-  float2* vec = vec_scratch ? reinterpret_cast<float2*>(p) : planner ? planner->data : nullptr; p += b_vec;
+  float2* vec = vec_scratch ? reinterpret_cast<float2*>(p) : planner ? planner->data.get() : nullptr; p += b_vec;
   float* slow = f.slowness ? reinterpret_cast<float*>(p) : nullptr; p += b_slow;
   uint32_t* cnt = counts_host ? reinterpret_cast<uint32_t*>(p) : counts_dev; p += b_cnt;
   uint32_t* extra_dev = reinterpret_cast<uint32_t*>(p); p += b_extra;
@@ -328,7 +317,7 @@ int flow_run(cs_engine* e, const cs_flow_desc& f, uint32_t* counts_dev, const ui
   uint8_t* blocked = f.blocked ? p : nullptr;
 
   hipStream_t st = e->stream;
-  HIP_OK_E(e, hipMemsetAsync(e->flow_scratch, 0, b_hdr, st));
+  HIP_OK_E(e, hipMemsetAsync(e->flow_scratch.get(), 0, b_hdr, st));
   HIP_OK_E(e, hipMemcpyAsync(goals, f.goals, bins, hipMemcpyHostToDevice, st));
   if (blocked) HIP_OK_E(e, hipMemcpyAsync(blocked, f.blocked, bins, hipMemcpyHostToDevice, st));
   if (slow) HIP_OK_E(e, hipMemcpyAsync(slow, f.slowness, bins * sizeof(float), hipMemcpyHostToDevice, st));

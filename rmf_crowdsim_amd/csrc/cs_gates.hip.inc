@@ -312,7 +312,7 @@ int gates_count(cs_engine* e, const cs_gate* gates, size_t n, double speed_max, 
   HIP_OK_E(e, hipMemcpyAsync(d_gates, gates, n * sizeof(cs_gate), hipMemcpyHostToDevice, e->stream));
   const uint32_t blocks = ((uint32_t)n + PAIRS_WAVES - 1u) / PAIRS_WAVES;
   hipLaunchKernelGGL(k_gate_count, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots,
-                     e->cell_start, e->sel_groups_dev, P, speed_max, d_gates, (uint32_t)n, d_counts, hdr);
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, speed_max, d_gates, (uint32_t)n, d_counts, hdr);
   HIP_OK_E(e, hipGetLastError());
   if (want_counts)
     HIP_OK_E(e, hipMemcpyAsync(part->counts.data(), d_counts, 2u * n * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
@@ -357,7 +357,7 @@ int gates_list(cs_engine* e, const GatePart& part, const cs_gate* gates, size_t 
   HIP_OK_E(e, hipMemcpyAsync(d_off, offsets.data(), (n + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
   const uint32_t blocks = ((uint32_t)n + PAIRS_WAVES - 1u) / PAIRS_WAVES;
   hipLaunchKernelGGL(k_gate_emit, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots,
-                     e->cell_start, e->sel_groups_dev, P, speed_max, d_gates, (uint32_t)n, d_off, hdr, keys, index, ss, us);
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, speed_max, d_gates, (uint32_t)n, d_off, hdr, keys, index, ss, us);
   HIP_OK_E(e, hipGetLastError());
   unsigned long long back[3];
   if (int rc = pairs_read_header(e, hdr, back)) return rc;  // (synchronised: the host staging may go)

@@ -119,19 +119,12 @@ static int hlp_field_eval(cs_engine* e) {
     for (const auto& kv : e->hlp_fields) {
       if (kv.first >= tab.size()) continue;
       tab[kv.first].d = kv.second.d;
-      tab[kv.first].vxy = kv.second.data;
+      tab[kv.first].vxy = kv.second.data.get();
       tab[kv.first].sampling = kv.second.sampling;
     }
     HIP_OK_E(e, hipStreamSynchronize(e->stream));  // (queued steps read the table that is replaced)
-    if (tab.size() > e->hlp_field_tab_cap) {
-      hipFree(e->hlp_field_tab);
-      e->hlp_field_tab = nullptr;
-      e->hlp_field_tab_cap = 0;
-      const size_t want = 2 * tab.size() + 8;
-      HIP_OK_E(e, hipMalloc(&e->hlp_field_tab, want * sizeof(HlpFieldDev)));
-      e->hlp_field_tab_cap = want;
-    }
-    HIP_OK_E(e, hipMemcpy(e->hlp_field_tab, tab.data(), tab.size() * sizeof(HlpFieldDev), hipMemcpyHostToDevice));
+    if (tab.size() > e->hlp_field_tab.count()) HIP_OK_E(e, e->hlp_field_tab.alloc(2 * tab.size() + 8));
+    HIP_OK_E(e, hipMemcpy(e->hlp_field_tab.get(), tab.data(), tab.size() * sizeof(HlpFieldDev), hipMemcpyHostToDevice));
     e->hlp_field_tab_n = (uint32_t)tab.size();  // (a planner registered later is no field, or sets the flag again)
     e->hlp_fields_dirty = false;
   }
@@ -139,7 +132,7 @@ static int hlp_field_eval(cs_engine* e) {
   // a CS_HLP_CALLBACK planner without a velocity function answers None: its slots of pref read zero as long as nobody
   // writes pref at all, which this kernel now does (slots change hands with every re-sort)
   if (e->any_silent_callback && !e->any_velocity_callback && n)
-    HIP_OK_E(e, hipMemsetAsync(e->pref, 0, (size_t)n * sizeof(float2), e->stream));
+    HIP_OK_E(e, hipMemsetAsync(e->pref.get(), 0, (size_t)n * sizeof(float2), e->stream));
   const AgentArrays& a = e->buf[e->cur];
   hipEvent_t t0 = nullptr, t1 = nullptr;
   if (e->hlp_field_timing && e->hlp_field_timed.size() < 4096u && hipEventCreate(&t0) == hipSuccess) {
@@ -151,8 +144,8 @@ static int hlp_field_eval(cs_engine* e) {
     }
   }
   hipLaunchKernelGGL(k_hlp_field, dim3(std::max(1u, (n + HLP_FIELD_BLOCK - 1u) / HLP_FIELD_BLOCK)), dim3(HLP_FIELD_BLOCK), 0,
-                     e->stream, e->gdev, a.cell, a.off, a.meta, n, e->ctr, e->groups_dev, (uint32_t)e->groups.size(),
-                     e->hlp_field_tab, e->hlp_field_tab_n, e->grid.offset_x, e->grid.offset_y, e->grid.cell_size, e->pref);
+                     e->stream, e->gdev, a.cell, a.off, a.meta, n, e->ctr.get(), e->groups_dev.get(), (uint32_t)e->groups.size(),
+                     e->hlp_field_tab.get(), e->hlp_field_tab_n, e->grid.offset_x, e->grid.offset_y, e->grid.cell_size, e->pref.get());
   if (t0) {
     e->hlp_field_timed.emplace_back(t0, t1);
     HIP_OK_E(e, hipEventRecord(t1, e->stream));
@@ -172,15 +165,14 @@ uint32_t cs_register_hlp_field(cs_engine* e, const cs_field_desc* raster, uint32
   f.d = *raster;
   f.sampling = sampling;
   const size_t bytes = (size_t)raster->nx * raster->ny * sizeof(float2);
-  if (hipMalloc(&f.data, bytes) != hipSuccess) {
+  if (f.data.alloc(bytes / sizeof(float2)) != hipSuccess) {
     (void)hipGetLastError();
     e->error = "hlp_field: out of device memory for the samples";
     return UINT32_MAX;
   }
   // (a buffer nothing queued reads yet: the blocking copy waits for no step)
-  if (hipMemcpy(f.data, vxy, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipMemcpy(f.data.get(), vxy, bytes, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipGetLastError();
-    hipFree(f.data);
     e->error = "hlp_field: HIP error while uploading the samples";
     return UINT32_MAX;
   }
@@ -189,7 +181,7 @@ uint32_t cs_register_hlp_field(cs_engine* e, const cs_field_desc* raster, uint32
   d.kind = CS_HLP_FIELD;
   e->hlps.push_back(d);
   const uint32_t handle = (uint32_t)e->hlps.size() - 1;
-  e->hlp_fields[handle] = f;
+  e->hlp_fields[handle] = std::move(f);
   e->hlp_fields_dirty = true;
   return handle;
 }
@@ -208,15 +200,15 @@ int cs_hlp_field_update(cs_engine* e, uint32_t hlp, const float* vxy) {
   hipSetDevice(e->device);
   HostHlpField& f = it->second;
   const size_t bytes = (size_t)f.d.nx * f.d.ny * sizeof(float2);
-  if (!f.stage) {
-    HIP_OK_E(e, hipHostMalloc(&f.stage, bytes));
+  if (!f.stage.get()) {
+    HIP_OK_E(e, f.stage.alloc(bytes / sizeof(float2)));
     HIP_OK_E(e, hipEventCreateWithFlags(&f.staged, hipEventDisableTiming));
   }
   if (f.stage_busy) HIP_OK_E(e, hipEventSynchronize(f.staged));  // (the upload of the update before this one)
   f.stage_busy = false;
-  std::memcpy(f.stage, vxy, bytes);
+  std::memcpy(f.stage.get(), vxy, bytes);
   // behind the steps already queued on the engine's stream, which sample the old values; in front of the next one
-  HIP_OK_E(e, hipMemcpyAsync(f.data, f.stage, bytes, hipMemcpyHostToDevice, e->stream));
+  HIP_OK_E(e, hipMemcpyAsync(f.data.get(), f.stage.get(), bytes, hipMemcpyHostToDevice, e->stream));
   HIP_OK_E(e, hipEventRecord(f.staged, e->stream));
   f.stage_busy = true;
   return 0;

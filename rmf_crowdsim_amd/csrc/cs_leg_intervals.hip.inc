@@ -260,7 +260,7 @@ int legiv_count(cs_engine* e, const cs_leg* legs, size_t n, double distance, dou
   HIP_OK_E(e, hipMemcpyAsync(d_legs, part->legs.data(), n * sizeof(cs_leg), hipMemcpyHostToDevice, e->stream));
   const uint32_t blocks = ((uint32_t)n + PAIRS_WAVES - 1u) / PAIRS_WAVES;
   hipLaunchKernelGGL(k_leg_intervals_count, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur],
-                     e->n_slots, e->cell_start, e->sel_groups_dev, P, distance, speed_max, d_legs, (uint32_t)n, d_counts,
+                     e->n_slots, e->cell_start.get(), e->sel_groups_dev.get(), P, distance, speed_max, d_legs, (uint32_t)n, d_counts,
                      hdr);
   HIP_OK_E(e, hipGetLastError());
   if (want_counts)
@@ -307,7 +307,7 @@ int legiv_list(cs_engine* e, const LegivPart& part, double distance, double spee
   HIP_OK_E(e, hipMemcpyAsync(d_off, offsets.data(), (n + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
   const uint32_t blocks = ((uint32_t)n + PAIRS_WAVES - 1u) / PAIRS_WAVES;
   hipLaunchKernelGGL(k_leg_intervals_emit, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur],
-                     e->n_slots, e->cell_start, e->sel_groups_dev, P, distance, speed_max, d_legs, (uint32_t)n, d_off, hdr,
+                     e->n_slots, e->cell_start.get(), e->sel_groups_dev.get(), P, distance, speed_max, d_legs, (uint32_t)n, d_off, hdr,
                      keys, index, s_ins, s_outs);
   HIP_OK_E(e, hipGetLastError());
   unsigned long long back[3];

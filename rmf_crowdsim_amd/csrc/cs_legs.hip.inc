@@ -256,7 +256,7 @@ int legs_run(cs_engine* e, const cs_leg* legs, size_t n, double distance, double
   HIP_OK_E(e, hipMemcpyAsync(d_legs, mine.data(), n * sizeof(cs_leg), hipMemcpyHostToDevice, e->stream));
   const uint32_t blocks = ((uint32_t)n + PAIRS_WAVES - 1u) / PAIRS_WAVES;
   hipLaunchKernelGGL(k_leg_conflicts, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots,
-                     e->cell_start, e->sel_groups_dev, P, distance, speed_max, d_legs, (uint32_t)n, d_hits);
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, distance, speed_max, d_legs, (uint32_t)n, d_hits);
   HIP_OK_E(e, hipGetLastError());
   HIP_OK_E(e, hipMemcpyAsync(rows->data(), d_hits, n * sizeof(cs_leg_hit), hipMemcpyDeviceToHost, e->stream));
   HIP_OK_E(e, hipStreamSynchronize(e->stream));  // (the host staging of the legs dies here)

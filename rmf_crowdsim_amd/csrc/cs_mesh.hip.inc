@@ -21,9 +21,8 @@ struct cs_mesh {
   bool use_rccl = false;     // halo records and spawn flags over RCCL from the engine itself
   bool has_host = false;     // a transport of the host's: instead of RCCL, or beside it for the gathers
   cs_mesh_host_transport host{};
-  unsigned char* stage_send[8] = {};  // pinned host copies of the halo buffers (host transport without RCCL)
-  unsigned char* stage_recv[8] = {};
-  size_t stage_bytes[8] = {};
+  PinnedBuf<unsigned char> stage_send[8];  // pinned host copies of the halo buffers (host transport without RCCL)
+  PinnedBuf<unsigned char> stage_recv[8];
   int device = 0;
   double density_per_cell = 16.0;
   uint64_t capacity_hint = 0;
@@ -32,13 +31,12 @@ struct cs_mesh {
   std::vector<cs_engine*> tiles;           // the local tiles
   std::vector<uint32_t> index_of;          // their global tile indices
   struct Buf {
-    void* send = nullptr;
-    void* recv = nullptr;
+    DevBytes send, recv;
     uint32_t cap = 0;
   };
   std::vector<std::array<Buf, 8>> bufs;
   hipStream_t stream = nullptr;
-  std::vector<int*> flag_bufs;  // device-side spawn flags, one vector per local tile
+  std::vector<DevBuf<int>> flag_bufs;  // device-side spawn flags, one vector per local tile
   size_t flag_cap = 0;
   bool has_sinks = false, host_planner = false, route_legs = false, recording = false;
   std::string error;
@@ -81,8 +79,8 @@ struct cs_mesh {
   uint32_t fail_word = 0;    // the failure word as the host last read it from the device (exact on a rank that waits)
   uint32_t diameter() const { return std::max(tiles_x, tiles_y) - 1u; }  // (eight neighbours each: Chebyshev distance)
   uint32_t step_tag() const { return (uint32_t)std::min<uint64_t>(step_index + 1u, 0xFFFFFFF0ull); }
-  int* agree_dev = nullptr;    // device int for the agreed check
-  int* agree_host = nullptr;   // pinned
+  DevBuf<int> agree_dev;       // device int for the agreed check
+  PinnedBuf<int> agree_host;   // pinned
 
   uint32_t n_tiles() const { return tiles_x * tiles_y; }
   void rect(uint32_t index, uint32_t* x0, uint32_t* x1, uint32_t* y0, uint32_t* y1) const {
@@ -174,18 +172,16 @@ static int mesh_set_buffers(cs_mesh* m, size_t local) {
   hipSetDevice(m->device);
   for (int d = 0; d < 8; ++d) {
     cs_mesh::Buf& b = m->bufs[local][d];
-    hipFree(b.send);
-    hipFree(b.recv);
     b = cs_mesh::Buf{};
     if (m->neighbour(m->index_of[local], d) < 0) continue;
     b.cap = mesh_halo_capacity(m, m->index_of[local], d);
     const size_t bytes = ((size_t)b.cap + 1u) * CS_HALO_RECORD_BYTES;
-    if (hipMalloc(&b.send, bytes) != hipSuccess || hipMalloc(&b.recv, bytes) != hipSuccess ||
-        hipMemsetAsync(b.send, 0, bytes, m->stream) != hipSuccess || hipMemsetAsync(b.recv, 0, bytes, m->stream) != hipSuccess) {
+    if (b.send.alloc(bytes) != hipSuccess || b.recv.alloc(bytes) != hipSuccess ||
+        hipMemsetAsync(b.send.get(), 0, bytes, m->stream) != hipSuccess || hipMemsetAsync(b.recv.get(), 0, bytes, m->stream) != hipSuccess) {
       m->error = "HIP error while allocating halo buffers";
       return 90;
     }
-    if (int rc = cs_halo_set_buffers(m->tiles[local], (uint32_t)d, b.send, b.recv, b.cap)) return m->fail(m->tiles[local], rc);
+    if (int rc = cs_halo_set_buffers(m->tiles[local], (uint32_t)d, b.send.get(), b.recv.get(), b.cap)) return m->fail(m->tiles[local], rc);
   }
   return 0;
 }
@@ -209,10 +205,12 @@ static int mesh_allgather(cs_mesh* m, const void* mine, size_t bytes, void* all)
   if (!bytes) return 0;
   cs_engine* e = m->tiles[0];
   hipSetDevice(m->device);
-  unsigned char* dev = nullptr;
+  DevBuf<unsigned char> mem;
   const size_t total = bytes * (size_t)m->n_ranks;
   int rc = 0;
-  if (hipMalloc((void**)&dev, bytes + total) != hipSuccess ||
+  const hipError_t got = mem.alloc(bytes + total);
+  unsigned char* dev = mem.get();
+  if (got != hipSuccess ||
       hipMemcpyAsync(dev, mine, bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess) {
     m->error = "HIP error in a gather of the mesh";
     rc = 90;
@@ -223,7 +221,6 @@ static int mesh_allgather(cs_mesh* m, const void* mine, size_t bytes, void* all)
     m->error = "HIP error in a gather of the mesh";
     rc = 90;
   }
-  hipFree(dev);
   return rc;
 }
 // element-wise maximum over the ranks, in place (host values)
@@ -232,9 +229,11 @@ static int mesh_allreduce_max(cs_mesh* m, int32_t* values, size_t n) {
   if (!n) return 0;
   cs_engine* e = m->tiles[0];
   hipSetDevice(m->device);
-  int* dev = nullptr;
+  DevBuf<int> mem;
   int rc = 0;
-  if (hipMalloc((void**)&dev, n * sizeof(int)) != hipSuccess ||
+  const hipError_t got = mem.alloc(n);
+  int* dev = mem.get();
+  if (got != hipSuccess ||
       hipMemcpyAsync(dev, values, n * sizeof(int), hipMemcpyHostToDevice, m->stream) != hipSuccess) {
     m->error = "HIP error in an all-reduce of the mesh";
     rc = 90;
@@ -245,7 +244,6 @@ static int mesh_allreduce_max(cs_mesh* m, int32_t* values, size_t n) {
     m->error = "HIP error in an all-reduce of the mesh";
     rc = 90;
   }
-  hipFree(dev);
   return rc;
 }
 // every rank's bytes, in rank order (sizes may differ: lengths first, then the padded payloads)
@@ -345,15 +343,12 @@ static int mesh_ids_room(cs_mesh* m, uint64_t n_new) {
 // pinned staging for the halo buffers of the local tile (after mesh_set_buffers)
 static int mesh_host_stage_alloc(cs_mesh* m) {
   for (int d = 0; d < 8; ++d) {
-    if (m->stage_send[d]) hipHostFree(m->stage_send[d]);
-    if (m->stage_recv[d]) hipHostFree(m->stage_recv[d]);
-    m->stage_send[d] = m->stage_recv[d] = nullptr;
-    m->stage_bytes[d] = 0;
+    m->stage_send[d].release();
+    m->stage_recv[d].release();
     const cs_mesh::Buf& b = m->bufs[0][d];
-    if (!b.send) continue;
-    m->stage_bytes[d] = ((size_t)b.cap + 1u) * CS_HALO_RECORD_BYTES;
-    if (hipHostMalloc((void**)&m->stage_send[d], m->stage_bytes[d]) != hipSuccess ||
-        hipHostMalloc((void**)&m->stage_recv[d], m->stage_bytes[d]) != hipSuccess) {
+    if (!b.send.get()) continue;
+    const size_t bytes = ((size_t)b.cap + 1u) * CS_HALO_RECORD_BYTES;
+    if (m->stage_send[d].alloc(bytes) != hipSuccess || m->stage_recv[d].alloc(bytes) != hipSuccess) {
       m->error = "HIP error while allocating the halo staging buffers";
       return 90;
     }
@@ -423,8 +418,7 @@ static int mesh_stop(cs_mesh* m, int local_rc, const std::string& local_error) {
 static int mesh_fail_word_now(cs_mesh* m, uint32_t raise, uint32_t* word) {
   cs_engine* e = m->tiles[0];
   hipSetDevice(m->device);
-  if (!m->agree_dev && (hipMalloc(&m->agree_dev, sizeof(int)) != hipSuccess ||
-                        hipHostMalloc(&m->agree_host, sizeof(int)) != hipSuccess))
+  if (!m->agree_dev.get() && (m->agree_dev.alloc(1) != hipSuccess || m->agree_host.alloc(1) != hipSuccess))
     return m->poison(90, "HIP error in the agreed check of the mesh");
   HaloBuffers8 recv, send;
   for (int d = 0; d < 8; ++d) {
@@ -432,12 +426,12 @@ static int mesh_fail_word_now(cs_mesh* m, uint32_t raise, uint32_t* word) {
     send.p[d] = e->halo[d].send;
     recv.cap[d] = send.cap[d] = e->halo[d].cap;
   }
-  hipLaunchKernelGGL(k_mesh_fail_merge, dim3(1), dim3(64), 0, e->stream, recv, send, e->ctr, m->step_tag(), raise,
-                     m->deferred_rc ? 1u : 0u, reinterpret_cast<uint32_t*>(m->agree_dev));
-  if (hipMemcpyAsync(m->agree_host, m->agree_dev, sizeof(int), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+  hipLaunchKernelGGL(k_mesh_fail_merge, dim3(1), dim3(64), 0, e->stream, recv, send, e->ctr.get(), m->step_tag(), raise,
+                     m->deferred_rc ? 1u : 0u, reinterpret_cast<uint32_t*>(m->agree_dev.get()));
+  if (hipMemcpyAsync(m->agree_host.get(), m->agree_dev.get(), sizeof(int), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
       hipStreamSynchronize(e->stream) != hipSuccess)
     return m->poison(90, "HIP error in the agreed check of the mesh");
-  *word = (uint32_t)*m->agree_host;
+  *word = (uint32_t)*m->agree_host.get();
   return 0;
 }
 
@@ -460,15 +454,14 @@ static int mesh_agree(cs_mesh* m, int local_rc, const std::string& local_error) 
   if (m->use_rccl) {
     cs_engine* e = m->tiles[0];
     hipSetDevice(m->device);
-    if (!m->agree_dev && (hipMalloc(&m->agree_dev, sizeof(int)) != hipSuccess ||
-                          hipHostMalloc(&m->agree_host, sizeof(int)) != hipSuccess))
+    if (!m->agree_dev.get() && (m->agree_dev.alloc(1) != hipSuccess || m->agree_host.alloc(1) != hipSuccess))
       return m->poison(90, "HIP error in the agreed check of the mesh");
-    hipLaunchKernelGGL(k_mesh_fail_flag, dim3(1), dim3(64), 0, m->stream, e->ctr, failed, m->agree_dev);
-    if (cs_allreduce_max_i32_rccl(e, m->agree_dev, 1) != 0) return m->poison(8, cs_last_error(e));
-    if (hipMemcpyAsync(m->agree_host, m->agree_dev, sizeof(int), hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+    hipLaunchKernelGGL(k_mesh_fail_flag, dim3(1), dim3(64), 0, m->stream, e->ctr.get(), failed, m->agree_dev.get());
+    if (cs_allreduce_max_i32_rccl(e, m->agree_dev.get(), 1) != 0) return m->poison(8, cs_last_error(e));
+    if (hipMemcpyAsync(m->agree_host.get(), m->agree_dev.get(), sizeof(int), hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess)
       return m->poison(90, "HIP error in the agreed check of the mesh");
-    failed = *m->agree_host;
+    failed = *m->agree_host.get();
   } else if (m->has_host) {
     int32_t v = failed;
     if (m->host.allreduce_max_i32(m->host.user, &v, 1)) return m->poison(91, "cs_mesh: the host transport's allreduce_max_i32 failed");
@@ -601,17 +594,15 @@ cs_mesh* cs_mesh_create(const cs_grid_desc* grid, const cs_mesh_desc* d) {
     const int key = (int)((h ^ (h >> 32)) & 0x3FFFFFFFull);
     int pair_host[2] = {key, -key};
     if (m->use_rccl) {
-      int* pair_dev = nullptr;
-      if (hipMalloc(&pair_dev, sizeof(pair_host)) != hipSuccess ||
-          hipMemcpyAsync(pair_dev, pair_host, sizeof(pair_host), hipMemcpyHostToDevice, m->stream) != hipSuccess)
+      DevBuf<int> pair_mem;
+      if (pair_mem.alloc(2) != hipSuccess) return bad(m, "cs_mesh_create: HIP error");
+      int* pair_dev = pair_mem.get();
+      if (hipMemcpyAsync(pair_dev, pair_host, sizeof(pair_host), hipMemcpyHostToDevice, m->stream) != hipSuccess)
         return bad(m, "cs_mesh_create: HIP error");
       const int rc = cs_allreduce_max_i32_rccl(m->tiles[0], pair_dev, 2);
       if (!rc && (hipMemcpyAsync(pair_host, pair_dev, sizeof(pair_host), hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-                  hipStreamSynchronize(m->stream) != hipSuccess)) {
-        hipFree(pair_dev);
+                  hipStreamSynchronize(m->stream) != hipSuccess))
         return bad(m, "cs_mesh_create: HIP error");
-      }
-      hipFree(pair_dev);
       if (rc) return bad(m, std::string("cs_mesh_create: ") + cs_last_error(m->tiles[0]));
     } else if (m->host.allreduce_max_i32(m->host.user, pair_host, 2)) {
       return bad(m, "cs_mesh_create: the host transport's allreduce_max_i32 failed");
@@ -630,20 +621,8 @@ void cs_mesh_destroy(cs_mesh* m) {
   hipSetDevice(m->device);
   if (m->stream) hipStreamSynchronize(m->stream);
   for (cs_engine* e : m->tiles) cs_destroy(e);
-  for (auto& eight : m->bufs)
-    for (auto& b : eight) {
-      hipFree(b.send);
-      hipFree(b.recv);
-    }
-  for (int* f : m->flag_bufs) hipFree(f);
-  hipFree(m->agree_dev);
-  if (m->agree_host) hipHostFree(m->agree_host);
-  for (int d = 0; d < 8; ++d) {
-    if (m->stage_send[d]) hipHostFree(m->stage_send[d]);
-    if (m->stage_recv[d]) hipHostFree(m->stage_recv[d]);
-  }
   if (m->stream) hipStreamDestroy(m->stream);
-  delete m;
+  delete m;  // (its members free the halo, staging and flag buffers: the device is current, the stream was waited for)
 }
 
 const char* cs_mesh_last_error(const cs_mesh* m) { return m ? m->error.c_str() : g_mesh_create_error.c_str(); }
@@ -790,10 +769,10 @@ static int mesh_exchange_local(cs_mesh* m, int* rc, std::string* why) {
   for (size_t k = 0; k < m->tiles.size(); ++k)
     for (int d = 0; d < 8; ++d) {
       const cs_mesh::Buf& b = m->bufs[k][d];
-      if (!b.send) continue;
+      if (!b.send.get()) continue;
       const int peer = m->local_of((uint32_t)m->neighbour(m->index_of[k], d));
       const cs_mesh::Buf& r = m->bufs[(size_t)peer][cs_mesh::opposite(d)];
-      if (hipMemcpyAsync(r.recv, b.send, ((size_t)b.cap + 1u) * CS_HALO_RECORD_BYTES, hipMemcpyDeviceToDevice, m->stream) !=
+      if (hipMemcpyAsync(r.recv.get(), b.send.get(), ((size_t)b.cap + 1u) * CS_HALO_RECORD_BYTES, hipMemcpyDeviceToDevice, m->stream) !=
           hipSuccess) {
         m->error = "HIP error in the halo exchange";
         return 90;
@@ -816,17 +795,17 @@ static int mesh_exchange_host(cs_mesh* m, int* rc, std::string* why) {
   size_t n = 0;
   for (int d = 0; d < 8; ++d) {
     const cs_mesh::Buf& b = m->bufs[0][d];
-    if (!b.send) continue;
-    if (hipMemcpyAsync(m->stage_send[d], b.send, m->stage_bytes[d], hipMemcpyDeviceToHost, m->stream) != hipSuccess) {
+    if (!b.send.get()) continue;
+    if (hipMemcpyAsync(m->stage_send[d].get(), b.send.get(), m->stage_send[d].bytes(), hipMemcpyDeviceToHost, m->stream) != hipSuccess) {
       m->error = "HIP error in the halo exchange";
       return 90;
     }
     peers[n] = m->neighbour(m->index_of[0], d);
     stag[n] = d;
     rtag[n] = cs_mesh::opposite(d);
-    sp[n] = m->stage_send[d];
-    rp[n] = m->stage_recv[d];
-    bytes[n] = m->stage_bytes[d];
+    sp[n] = m->stage_send[d].get();
+    rp[n] = m->stage_recv[d].get();
+    bytes[n] = m->stage_send[d].bytes();
     ++n;
   }
   if (hipStreamSynchronize(m->stream) != hipSuccess) {
@@ -836,8 +815,8 @@ static int mesh_exchange_host(cs_mesh* m, int* rc, std::string* why) {
   if (m->host.exchange(m->host.user, n, peers, stag, rtag, sp, rp, bytes)) return mesh_host_fail(m, "exchange");
   for (int d = 0; d < 8; ++d) {
     const cs_mesh::Buf& b = m->bufs[0][d];
-    if (!b.send) continue;
-    if (hipMemcpyAsync(b.recv, m->stage_recv[d], m->stage_bytes[d], hipMemcpyHostToDevice, m->stream) != hipSuccess) {
+    if (!b.send.get()) continue;
+    if (hipMemcpyAsync(b.recv.get(), m->stage_recv[d].get(), m->stage_recv[d].bytes(), hipMemcpyHostToDevice, m->stream) != hipSuccess) {
       m->error = "HIP error in the halo exchange";
       return 90;
     }
@@ -937,24 +916,26 @@ int cs_mesh_step(cs_mesh* m, double dt, cs_step_report* report) {
     hipSetDevice(m->device);
     if (ns > m->flag_cap || m->flag_bufs.size() != m->tiles.size()) {
       hipStreamSynchronize(m->stream);
-      for (int* f : m->flag_bufs) hipFree(f);
-      m->flag_bufs.assign(m->tiles.size(), nullptr);
-      m->flag_cap = 2 * ns + 64;
-      for (int*& f : m->flag_bufs)
-        if (hipMalloc(&f, m->flag_cap * sizeof(int)) != hipSuccess || hipMemsetAsync(f, 0, m->flag_cap * sizeof(int), m->stream) != hipSuccess) {
+      m->flag_bufs.clear();
+      m->flag_bufs.resize(m->tiles.size());
+      m->flag_cap = 0;
+      const size_t cap = 2 * ns + 64;
+      for (DevBuf<int>& f : m->flag_bufs)
+        if (f.alloc(cap) != hipSuccess || hipMemsetAsync(f.get(), 0, cap * sizeof(int), m->stream) != hipSuccess) {
           m->error = "HIP error while allocating spawn flags";
           return fatal(90);
         }
+      m->flag_cap = cap;
     }
     if (!host_flags) {  // flags stay on the device (in-process form)
       for (size_t k = 0; k < m->tiles.size(); ++k)
-        if (!rc) mesh_note(m, m->tiles[k], cs_spawn_probe_dev(m->tiles[k], dt, m->flag_bufs[k], ns), &rc, &why);
+        if (!rc) mesh_note(m, m->tiles[k], cs_spawn_probe_dev(m->tiles[k], dt, m->flag_bufs[k].get(), ns), &rc, &why);
       if (!rc)
         for (size_t k = 1; k < m->tiles.size(); ++k)
-          hipLaunchKernelGGL(k_i32_max, dim3((uint32_t)((ns + 255) / 256)), dim3(256), 0, m->stream, m->flag_bufs[0],
-                             m->flag_bufs[k], (uint32_t)ns);
+          hipLaunchKernelGGL(k_i32_max, dim3((uint32_t)((ns + 255) / 256)), dim3(256), 0, m->stream, m->flag_bufs[0].get(),
+                             m->flag_bufs[k].get(), (uint32_t)ns);
       for (cs_engine* e : m->tiles)
-        if (!rc) mesh_note(m, e, cs_spawn_commit_dev(e, m->flag_bufs[0], ns), &rc, &why);
+        if (!rc) mesh_note(m, e, cs_spawn_commit_dev(e, m->flag_bufs[0].get(), ns), &rc, &why);
     } else {
       std::vector<uint8_t> all(std::max<size_t>(ns, 1), 0), mine(std::max<size_t>(ns, 1), 0);
       for (cs_engine* e : m->tiles) {
@@ -971,10 +952,10 @@ int cs_mesh_step(cs_mesh* m, double dt, cs_step_report* report) {
       } else if (m->distributed) {  // OR over the ranks: one small all-reduce (max) of device ints
         std::vector<int> host(std::max<size_t>(ns, 1), 0);
         for (size_t s = 0; s < ns; ++s) host[s] = all[s];
-        if (hipMemcpyAsync(m->flag_bufs[0], host.data(), ns * sizeof(int), hipMemcpyHostToDevice, m->stream) != hipSuccess)
+        if (hipMemcpyAsync(m->flag_bufs[0].get(), host.data(), ns * sizeof(int), hipMemcpyHostToDevice, m->stream) != hipSuccess)
           return fatal(90);
-        if (int r = cs_allreduce_max_i32_rccl(m->tiles[0], m->flag_bufs[0], ns)) return fatal(m->fail(m->tiles[0], r));
-        if (hipMemcpyAsync(host.data(), m->flag_bufs[0], ns * sizeof(int), hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        if (int r = cs_allreduce_max_i32_rccl(m->tiles[0], m->flag_bufs[0].get(), ns)) return fatal(m->fail(m->tiles[0], r));
+        if (hipMemcpyAsync(host.data(), m->flag_bufs[0].get(), ns * sizeof(int), hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
             hipStreamSynchronize(m->stream) != hipSuccess)
           return fatal(90);
         for (size_t s = 0; s < ns; ++s) all[s] = host[s] ? 1 : 0;
@@ -1121,7 +1102,7 @@ uint64_t cs_mesh_exchange_bytes(const cs_mesh* m) {
   uint64_t bytes = 0;
   for (const auto& eight : m->bufs)
     for (const auto& b : eight)
-      if (b.send) bytes += ((uint64_t)b.cap + 1u) * CS_HALO_RECORD_BYTES;
+      if (b.send.get()) bytes += ((uint64_t)b.cap + 1u) * CS_HALO_RECORD_BYTES;
   return bytes;
 }
 

@@ -402,46 +402,26 @@ PairsArgs pairs_args(const cs_engine* e, double distance, const cs_selection* sa
 // names close_pairs whichever call ran out, as it did before the queries shared it (error strings stay byte for byte).
 struct PairsScratch {
   cs_engine* e;
-  void* temp = nullptr;
+  DevBytes temp;
   explicit PairsScratch(cs_engine* e_) : e(e_) {}
-  PairsScratch(const PairsScratch&) = delete;
-  PairsScratch& operator=(const PairsScratch&) = delete;
   ~PairsScratch() {
-    if (!temp) return;
-    hipStreamSynchronize(e->stream);
-    hipFree(temp);
+    if (temp.get()) hipStreamSynchronize(e->stream);  // (then `temp` frees it)
   }
+  // One get per instance: a second one would free the first one's `temp` without waiting for the stream.
   void* get(size_t need, bool own = false) {
-    if (own || need > PAIRS_SCRATCH_KEEP) {
-      if (hipMalloc(&temp, need) != hipSuccess) {
-        temp = nullptr;
-        e->error = "close_pairs: out of device memory for the list of pairs";
-        return nullptr;
-      }
-      return temp;
+    const bool kept = !own && need <= PAIRS_SCRATCH_KEEP;
+    if ((kept ? e->pairs_scratch.reserve(e->stream, need) : temp.alloc(need)) != hipSuccess) {
+      e->error = "close_pairs: out of device memory for the list of pairs";
+      return nullptr;
     }
-    if (need > e->pairs_scratch_bytes) {
-      if (e->pairs_scratch) {
-        hipStreamSynchronize(e->stream);
-        hipFree(e->pairs_scratch);
-      }
-      e->pairs_scratch = nullptr;
-      e->pairs_scratch_bytes = 0;
-      if (hipMalloc(&e->pairs_scratch, need) != hipSuccess) {
-        e->pairs_scratch = nullptr;
-        e->error = "close_pairs: out of device memory for the list of pairs";
-        return nullptr;
-      }
-      e->pairs_scratch_bytes = need;
-    }
-    return e->pairs_scratch;
+    return kept ? e->pairs_scratch.get() : temp.get();
   }
 };
 
 // the 256-byte header of a count or a listing, in the by-id scratch, zeroed on the stream
 int pairs_header(cs_engine* e, unsigned long long** hdr) {
   if (int rc = write_scratch_reserve(e, 256u)) return rc;
-  *hdr = static_cast<unsigned long long*>(e->write_scratch);
+  *hdr = static_cast<unsigned long long*>(e->write_scratch.get());
   HIP_OK_E(e, hipMemsetAsync(*hdr, 0, 256u, e->stream));
   return 0;
 }
@@ -488,7 +468,7 @@ int pairs_band_run(cs_engine* e, const PairsArgs& P, uint32_t edges, uint32_t ti
   const uint32_t n = e->n_slots;
   HIP_OK_E(e, hipMemsetAsync(d_count, 0, sizeof(uint32_t), e->stream));
   hipLaunchKernelGGL(k_pairs_band, dim3((n + PAIRS_BLOCK - 1u) / PAIRS_BLOCK), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev,
-                     e->buf[e->cur], n, e->cell_start, e->sel_groups_dev, P, edges, tile_index, d_rec, d_slot, n, d_count);
+                     e->buf[e->cur], n, e->cell_start.get(), e->sel_groups_dev.get(), P, edges, tile_index, d_rec, d_slot, n, d_count);
   HIP_OK_E(e, hipGetLastError());
   uint32_t found = 0;
   HIP_OK_E(e, hipMemcpyAsync(&found, d_count, sizeof found, hipMemcpyDeviceToHost, e->stream));

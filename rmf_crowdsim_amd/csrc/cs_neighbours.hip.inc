@@ -253,7 +253,7 @@ int neigh_run(cs_engine* e, const PairsArgs& P, uint64_t min_count, size_t want,
   const uint32_t blocks = (n + PAIRS_BLOCK - 1u) / PAIRS_BLOCK;
   if (!want) {
     hipLaunchKernelGGL(k_neighbours<NEIGH_COUNT>, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n,
-                       e->cell_start, e->sel_groups_dev, P, (unsigned long long)min_count, hdr, (unsigned long long*)nullptr,
+                       e->cell_start.get(), e->sel_groups_dev.get(), P, (unsigned long long)min_count, hdr, (unsigned long long*)nullptr,
                        (NeighRow*)nullptr, (uint32_t*)nullptr, 0u);
     HIP_OK_E(e, hipGetLastError());
     unsigned long long found = 0;
@@ -265,7 +265,7 @@ int neigh_run(cs_engine* e, const PairsArgs& P, uint64_t min_count, size_t want,
   NeighArrays A;
   if (int rc = neigh_arrays(&sc, n, want, true, &A)) return rc;
   hipLaunchKernelGGL(k_neighbours<NEIGH_LIST>, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n,
-                     e->cell_start, e->sel_groups_dev, P, (unsigned long long)min_count, hdr, A.keys, A.rows, (uint32_t*)nullptr,
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, (unsigned long long)min_count, hdr, A.keys, A.rows, (uint32_t*)nullptr,
                      n);
   HIP_OK_E(e, hipGetLastError());
   unsigned long long back[3];
@@ -291,19 +291,14 @@ void neigh_copy_out(const cs_engine* ids_of, const std::vector<cs_neighbour_stat
 // mesh: the staged rows and the band of one tile, on its device for the length of the call
 struct NeighHold {
   cs_engine* e = nullptr;
-  void* mem = nullptr;
+  DevBytes mem;
   uint32_t n = 0, n_band = 0;
   uint32_t* stage_id = nullptr;
   NeighRow* rows = nullptr;
   PairsBandRec* band = nullptr;
   uint32_t* band_slot = nullptr;
-  NeighHold() = default;
-  NeighHold(const NeighHold&) = delete;
-  NeighHold& operator=(const NeighHold&) = delete;
   ~NeighHold() {
-    if (!mem) return;
-    hipStreamSynchronize(e->stream);
-    hipFree(mem);
+    if (mem.get()) hipStreamSynchronize(e->stream);  // (then `mem` frees it)
   }
 };
 
@@ -321,12 +316,11 @@ int neigh_stage(cs_engine* e, const PairsArgs& P, uint32_t edges, uint32_t tile_
   const bool want_band = edges && P.dist2 > 0.0;
   const size_t b_id = sel_up((size_t)n * sizeof(uint32_t)), b_rows = sel_up((size_t)n * sizeof(NeighRow));
   const size_t b_band = want_band ? sel_up((size_t)n * sizeof(PairsBandRec)) : 0u, b_slot = want_band ? b_id : 0u;
-  if (hipMalloc(&h->mem, 256u + b_id + b_rows + b_band + b_slot) != hipSuccess) {
-    h->mem = nullptr;
+  if (h->mem.alloc(256u + b_id + b_rows + b_band + b_slot) != hipSuccess) {
     e->error = "agent_neighbours: out of device memory";
     return 90;
   }
-  unsigned char* p = static_cast<unsigned char*>(h->mem);
+  unsigned char* p = static_cast<unsigned char*>(h->mem.get());
   uint32_t* d_count = reinterpret_cast<uint32_t*>(p);
   h->stage_id = reinterpret_cast<uint32_t*>(p + 256u);
   h->rows = reinterpret_cast<NeighRow*>(p + 256u + b_id);
@@ -334,7 +328,7 @@ int neigh_stage(cs_engine* e, const PairsArgs& P, uint32_t edges, uint32_t tile_
   h->band_slot = reinterpret_cast<uint32_t*>(p + 256u + b_id + b_rows + b_band);
   const uint32_t blocks = (n + PAIRS_BLOCK - 1u) / PAIRS_BLOCK;
   hipLaunchKernelGGL(k_neighbours<NEIGH_STAGE>, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n,
-                     e->cell_start, e->sel_groups_dev, P, 0ull, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, 0ull, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
                      h->rows, h->stage_id, n);
   HIP_OK_E(e, hipGetLastError());
   if (!want_band) {

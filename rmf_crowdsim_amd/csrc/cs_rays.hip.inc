@@ -267,7 +267,7 @@ int rays_run(cs_engine* e, const cs_ray* rays, size_t n, double radius, const cs
   HIP_OK_E(e, hipMemcpyAsync(d_rays, mine.data(), n * sizeof(cs_ray), hipMemcpyHostToDevice, e->stream));
   const uint32_t blocks = ((uint32_t)n + PAIRS_WAVES - 1u) / PAIRS_WAVES;
   hipLaunchKernelGGL(k_cast_rays, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots,
-                     e->cell_start, e->sel_groups_dev, P, radius + e->grid.cell_size, d_rays, (uint32_t)n, d_hits);
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, radius + e->grid.cell_size, d_rays, (uint32_t)n, d_hits);
   HIP_OK_E(e, hipGetLastError());
   HIP_OK_E(e, hipMemcpyAsync(rows->data(), d_hits, n * sizeof(cs_ray_hit), hipMemcpyDeviceToHost, e->stream));
   HIP_OK_E(e, hipStreamSynchronize(e->stream));  // (the host staging of the rays dies here)

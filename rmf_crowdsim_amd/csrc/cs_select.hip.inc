@@ -237,17 +237,12 @@ int sel_begin(cs_engine* e) {
     const HostGroup& g = e->groups[i];  // (NOT the GroupDev copy: that one forgets a removed sink)
     host[i] = SelGroupDev{g.sink >= 0 ? (uint32_t)g.sink : UINT32_MAX, g.hlp, g.lp};
   }
-  if (n > e->sel_groups_cap) {
+  if (n > e->sel_groups_dev.count()) {
     HIP_OK_E(e, hipStreamSynchronize(e->stream));
-    hipFree(e->sel_groups_dev);
-    e->sel_groups_dev = nullptr;
-    e->sel_groups_cap = 0;
-    const size_t cap = std::max<size_t>(1024, 2 * n);
-    HIP_OK_E(e, hipMalloc(&e->sel_groups_dev, cap * sizeof(SelGroupDev)));
-    e->sel_groups_cap = cap;
+    HIP_OK_E(e, e->sel_groups_dev.alloc(std::max<size_t>(1024, 2 * n)));
   }
   if (n) {
-    HIP_OK_E(e, hipMemcpyAsync(e->sel_groups_dev, host.data(), n * sizeof(SelGroupDev), hipMemcpyHostToDevice, e->stream));
+    HIP_OK_E(e, hipMemcpyAsync(e->sel_groups_dev.get(), host.data(), n * sizeof(SelGroupDev), hipMemcpyHostToDevice, e->stream));
     HIP_OK_E(e, hipStreamSynchronize(e->stream));  // (the host staging dies here)
   }
   e->sel_groups_dirty = false;
@@ -269,15 +264,15 @@ int sel_run(cs_engine* e, const cs_selection& s, size_t want, std::vector<uint32
   const size_t b_hdr = 256u, b_keys = sel_up((size_t)n * sizeof(uint32_t));
   const size_t b_hist = sel_up(IDS_RADIX * tiles_max * sizeof(uint32_t));
   if (int rc = write_scratch_reserve(e, b_hdr + 2u * b_keys + b_hist)) return rc;
-  unsigned char* sc = static_cast<unsigned char*>(e->write_scratch);
+  unsigned char* sc = static_cast<unsigned char*>(e->write_scratch.get());
   uint32_t* hdr = reinterpret_cast<uint32_t*>(sc);
   uint32_t* keys = reinterpret_cast<uint32_t*>(sc + b_hdr);
   uint32_t* other = reinterpret_cast<uint32_t*>(sc + b_hdr + b_keys);
   uint32_t* hist = reinterpret_cast<uint32_t*>(sc + b_hdr + 2u * b_keys);
   HIP_OK_E(e, hipMemsetAsync(hdr, 0, 2u * sizeof(uint32_t), e->stream));
   hipLaunchKernelGGL(k_select, dim3((n + SEL_SELECT_BLOCK - 1u) / SEL_SELECT_BLOCK), dim3(SEL_SELECT_BLOCK), 0, e->stream,
-                     e->gdev, e->buf[e->cur], n, e->ctr, e->tile ? 1u : 0u, (e->tile && e->ghosts_present) ? 1u : 0u,
-                     e->sel_groups_dev, (uint32_t)e->groups.size(), e->grid.offset_x, e->grid.offset_y, e->grid.cell_size, s,
+                     e->gdev, e->buf[e->cur], n, e->ctr.get(), e->tile ? 1u : 0u, (e->tile && e->ghosts_present) ? 1u : 0u,
+                     e->sel_groups_dev.get(), (uint32_t)e->groups.size(), e->grid.offset_x, e->grid.offset_y, e->grid.cell_size, s,
                      keys, n, hdr);
   HIP_OK_E(e, hipGetLastError());
   uint32_t back[2] = {0u, 0u};
@@ -338,7 +333,7 @@ int sel_count(cs_engine* e, const cs_selection* sels, size_t n_sel, uint64_t* co
   if (!n || !n_sel) return 0;
   const size_t b_sels = sel_up(n_sel * sizeof(cs_selection)), b_cnt = sel_up(n_sel * sizeof(uint32_t));
   if (int rc = write_scratch_reserve(e, b_sels + b_cnt)) return rc;
-  unsigned char* sc = static_cast<unsigned char*>(e->write_scratch);
+  unsigned char* sc = static_cast<unsigned char*>(e->write_scratch.get());
   cs_selection* d_sels = reinterpret_cast<cs_selection*>(sc);
   uint32_t* d_cnt = reinterpret_cast<uint32_t*>(sc + b_sels);
   uint32_t want_vel = 0u;
@@ -350,8 +345,8 @@ int sel_count(cs_engine* e, const cs_selection* sels, size_t n_sel, uint64_t* co
   if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || n_cu <= 0) n_cu = 256;
   const uint64_t per_block = (uint64_t)SEL_BLOCK * SEL_ITEMS;
   const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1u) / per_block, (uint64_t)n_cu * 4u));
-  hipLaunchKernelGGL(k_select_count, dim3(blocks), dim3(SEL_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n, e->ctr,
-                     e->tile ? 1u : 0u, (e->tile && e->ghosts_present) ? 1u : 0u, e->sel_groups_dev, (uint32_t)e->groups.size(),
+  hipLaunchKernelGGL(k_select_count, dim3(blocks), dim3(SEL_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], n, e->ctr.get(),
+                     e->tile ? 1u : 0u, (e->tile && e->ghosts_present) ? 1u : 0u, e->sel_groups_dev.get(), (uint32_t)e->groups.size(),
                      e->grid.offset_x, e->grid.offset_y, e->grid.cell_size, d_sels, (uint32_t)n_sel, want_vel, d_cnt);
   HIP_OK_E(e, hipGetLastError());
   std::vector<uint32_t> back(n_sel);

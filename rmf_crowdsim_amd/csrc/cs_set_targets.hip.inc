@@ -122,8 +122,8 @@ int targets_probe(cs_engine* e, const uint64_t* ids, const double* goals, size_t
     std::memcpy(host.data() + b_keyof, goals, 2 * n * sizeof(double));
     HIP_OK_E(e, hipMemcpyAsync(d_keyof, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_target_probe, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, e->stream, e->gdev, e->view(e->cur),
-                       e->n_slots, e->groups_dev, (uint32_t)e->groups.size(), e->any_route_hlp ? e->hlp_scale_dev : nullptr,
-                       e->any_route_hlp ? e->route_book_dev : nullptr, e->route_book_size ? e->route_book_size - 1u : 0u,
+                       e->n_slots, e->groups_dev.get(), (uint32_t)e->groups.size(), e->any_route_hlp ? e->hlp_scale_dev.get() : nullptr,
+                       e->any_route_hlp ? e->route_book_dev.get() : nullptr, e->route_book_size ? e->route_book_size - 1u : 0u,
                        e->grid.offset_x, e->grid.offset_y, e->grid.cell_size, t->ids.d_slot, (uint32_t)nk, d_keyof, d_goals,
                        (uint32_t)n, d_recs);
     HIP_OK_E(e, hipGetLastError());

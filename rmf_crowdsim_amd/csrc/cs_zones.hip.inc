@@ -372,7 +372,7 @@ int zone_count(cs_engine* e, const cs_zone* zones, size_t n, const double* verti
   HIP_OK_E(e, hipMemsetAsync(d_counts, 0, n * sizeof(uint64_t), e->stream));
   const uint32_t blocks = (items + PAIRS_WAVES - 1u) / PAIRS_WAVES;
   hipLaunchKernelGGL(k_zone_count, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots,
-                     e->cell_start, e->sel_groups_dev, P, t.zones, t.item0, (uint32_t)n, items, part->group_rows, t.vertices,
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, t.zones, t.item0, (uint32_t)n, items, part->group_rows, t.vertices,
                      d_counts, hdr);
   HIP_OK_E(e, hipGetLastError());
   if (want_counts)
@@ -421,7 +421,7 @@ int zone_list(cs_engine* e, const ZonePart& part, const double* vertices_xy, siz
   HIP_OK_E(e, hipMemsetAsync(d_cur, 0, n * sizeof(uint32_t), e->stream));
   const uint32_t blocks = (items + PAIRS_WAVES - 1u) / PAIRS_WAVES;
   hipLaunchKernelGGL(k_zone_emit, dim3(blocks), dim3(PAIRS_BLOCK), 0, e->stream, e->gdev, e->buf[e->cur], e->n_slots,
-                     e->cell_start, e->sel_groups_dev, P, t.zones, t.item0, (uint32_t)n, items, part.group_rows, t.vertices,
+                     e->cell_start.get(), e->sel_groups_dev.get(), P, t.zones, t.item0, (uint32_t)n, items, part.group_rows, t.vertices,
                      d_off, d_cur, hdr, keys);
   HIP_OK_E(e, hipGetLastError());
   unsigned long long back[3];
